@@ -8,7 +8,13 @@ DESIGN.md 4.9).  Default workload = the north star: 1M x 4 KiB bodies per GPU
 (weak scaling), synthetic splitmix64 bytes generated on the device.  Other
 BASELINE configs: --config c1 | c2 | c3 | c4.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  N>1: one process per
+Launch: python bench.py [--gpus N --steps K --warmup W].  A plain run does only
+what the headline figure needs: set up, warm up, time the K steps, print the line.
+--dump-outputs DIR also writes the CRCs of the last timed step (DIR/crc32.npy).
+--full adds every other leg after the timed steps: the per-rank CRC check against
+the reference crc.c, the per-step median pass, the stream-read probe, live PMC
+traffic, host-inclusive, receive ring, lifted-cap frames, drop-in latency and the
+CPU baseline (each with its own --no-... switch).  N>1: one process per
 GPU under torch.distributed.run -- either the driver's own launch, or, when
 WORLD_SIZE is not set, bench.py starts that launcher as a CHILD process itself
 (before importing torch or touching a GPU) and exits with its code.  RCCL is
@@ -78,6 +84,15 @@ def parse():
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                    help="N>1 barrier backend: nccl (= RCCL over xGMI, the product); gloo only to rehearse "
                         "several ranks on one GPU")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg: the per-rank CRC check against the "
+                        "reference crc.c, the per-step median pass, the stream-read probe, live PMC traffic, "
+                        "host-inclusive, receive ring, lifted-cap frames, drop-in latency, CPU baseline "
+                        "(the --no-... switches below drop single legs of it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the CRCs the last timed step computed to DIR/crc32.npy (float64, exact for "
+                        "32-bit values; N > 1: DIR/crc32_rank<r>.npy per rank); batches over the size cap "
+                        "are written as a fixed seeded sample (dump_sample_index)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-host-inclusive", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline work (multi-thread leg)")
@@ -163,6 +178,30 @@ def _loguniform_lengths(n, seed, lo=64, hi=65536):
     u = (z >> np.uint64(11)).astype(np.float64) * (1.0 / (1 << 53))
     ln = np.floor(lo * np.exp(u * np.log(hi / lo))).astype(np.int64)
     return np.clip(ln, lo, hi).astype(np.uint32)
+
+
+# --dump-outputs: at most this many CRCs over all ranks (float64: 32 MiB in all).
+DUMP_MAX_VALUES = 1 << 22
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_sample_index(n: int, world: int):
+    """Which of a rank's n CRCs --dump-outputs writes: None = all of them, else a
+    sorted sample of DUMP_MAX_VALUES // world indices, the same in every run."""
+    cap = max(1, DUMP_MAX_VALUES // max(1, world))
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(dirname: str, crc, world: int, rank: int) -> str:
+    """Write one rank's CRCs (uint32 values, in batch order) as float64 .npy."""
+    crc = np.asarray(crc).view(np.uint32)
+    idx = dump_sample_index(len(crc), world)
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "crc32.npy" if world == 1 else f"crc32_rank{rank}.npy")
+    np.save(path, (crc if idx is None else crc[idx]).astype(np.float64))
+    return path
 
 
 def log(msg: str):
@@ -846,6 +885,8 @@ def main():
         barrier(dist, device)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    # what the last timed step wrote, kept before any later leg reuses w.out
+    last_out = w.out.clone() if args.dump_outputs else None
     if args.step_events:
         step_s = [evs[k].elapsed_time(evs[k + 1]) / 1e3 for k in range(args.steps)]
     else:
@@ -853,7 +894,7 @@ def main():
     kernel_s = sum(step_s) / args.steps  # avg launch duration on the kernel's stream
     median_s = float(np.median(step_s))
     median_src = "timed pass, an event after every step" if args.step_events else None
-    if not args.step_events:
+    if args.full and not args.step_events:
         mev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         # The clock drops during the sync above and takes ~20 launches to ramp
         # back (a median over 5 re-warm launches read 16 % slow): ~0.3 s of
@@ -869,20 +910,25 @@ def main():
         median_src = "second K-step pass with an event after every step (each adds a marker between launches)"
     tr = rank_timing(dist, device, wall, kernel_s, median_s, w.total)
     tmax, total_bytes = tr["wall"], tr["total"]
+    if last_out is not None:
+        log("wrote " + dump_outputs(args.dump_outputs, last_out.cpu().numpy(), world, rank))
     if args.traffic_child:
         # live_traffic's PMC child: only the product's steps in the trace (no
         # stream probe, unbounded call or CRC check launches to tell apart)
         if dist:
             dist.destroy_process_group()
         return
-    # every rank checks its own first bodies (outside the timed region)
-    log("per-rank CRC check against the reference crc.c")
-    chk = reduce_crc_check(dist, device, rank_crc_check(*rank_check_sample(w),
-                                                        threads=max(1, effective_cpus()[0] // max(1, world))), world)
+    chk = None
+    if args.full:
+        # every rank checks its own first bodies (outside the timed region)
+        log("per-rank CRC check against the reference crc.c")
+        chk = reduce_crc_check(dist, device,
+                               rank_crc_check(*rank_check_sample(w),
+                                              threads=max(1, effective_cpus()[0] // max(1, world))), world)
 
     extra = {}
     cpu = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         log("stream-read probe")
         extra["stream_read_probe"] = stream_read_probe(w, args.steps)
         if not args.no_host_inclusive:
@@ -906,7 +952,7 @@ def main():
     if rank == 0:
         achieved = w.algo_bytes / tr["kernel_s"] / 1e9
         traffic_rec, traffic_src = None, "not measured"
-        if world == 1 and not args.no_live_traffic:
+        if args.full and world == 1 and not args.no_live_traffic:
             log("measuring HBM traffic (two rocprofv3 PMC passes)")
             traffic_rec, traffic_src = live_traffic(args, w.algo_bytes)
         if traffic_rec is not None:
@@ -944,6 +990,8 @@ def main():
             },
             "roofline": {
                 **roofline_fields(w.algo_bytes, tr, world),
+                # a plain run has no per-step times (--full or --step-events 1 measure them)
+                **({} if median_src else {"median_launch_us": None}),
                 "traffic": traffic,
                 "traffic_source": traffic_src,
                 "traffic_detail": traffic_rec,
@@ -970,16 +1018,18 @@ def main():
                                                        / extra["stream_read_probe"]["rows_dealing_GBps"], 4)
                                                  if "rows_dealing_GBps" in extra.get("stream_read_probe", {}) else None),
             },
-            # the reference crc.c on the host's cores: timed on rank 0 at N = 1 only
-            # (an N > 1 run shares the host among N ranks)
-            "cpu_baseline": cpu if world == 1 else None,
-            # every rank's first bodies against the reference crc.c (VERDICT r04 #5)
-            "ranks_crc_ok": chk["ranks_ok"] == world,
-            "ranks_crc_check": chk,
             "prewarm": {"seconds": args.prewarm_s, "steps": prewarm_steps},
             "device": rpc_amd.device_info(),
-            "extra": extra,
+            "full": args.full,
         }
+        if args.full:
+            # the reference crc.c on the host's cores: timed on rank 0 at N = 1 only
+            # (an N > 1 run shares the host among N ranks)
+            line["cpu_baseline"] = cpu if world == 1 else None
+            # every rank's first bodies against the reference crc.c (VERDICT r04 #5)
+            line["ranks_crc_ok"] = chk["ranks_ok"] == world
+            line["ranks_crc_check"] = chk
+            line["extra"] = extra
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -92,6 +92,51 @@ def test_gpus2_per_rank_crc_check():
     assert c["ranks_ok"] == 1 and c["mismatches"] == 1 and c["bodies_checked"] == 128
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full is off unless asked for; --dump-outputs takes the directory."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup, a.config) == (False, None, 7, 2, "ns")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_exact_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: 32-bit CRCs survive the float64 file bit for bit, a
+    batch over the cap is written as the same sorted sample every time, and the
+    files of all ranks together stay below 64 MB."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    crc = np.array([0, 1, 0xCBF43926, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF], dtype=np.uint32)
+    p = bench.dump_outputs(str(tmp_path / "a"), crc.view(np.int32), 1, 0)  # the device buffer is int32
+    assert os.path.basename(p) == "crc32.npy"
+    got = np.load(p)
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), crc)
+    assert got.tolist() == [float(int(x)) for x in crc]
+    assert os.path.basename(bench.dump_outputs(str(tmp_path / "a"), crc, 2, 1)) == "crc32_rank1.npy"
+
+    assert bench.dump_sample_index(bench.DUMP_MAX_VALUES, 1) is None
+    n = bench.DUMP_MAX_VALUES + 5
+    i1, i2 = bench.dump_sample_index(n, 1), bench.dump_sample_index(n, 1)
+    assert np.array_equal(i1, i2) and len(i1) == bench.DUMP_MAX_VALUES
+    assert np.all(np.diff(i1) > 0) and i1[0] >= 0 and i1[-1] < n
+    for world in (1, 2, 8):
+        assert world * (bench.DUMP_MAX_VALUES // world) * 8 + world * 128 <= 64_000_000
+    big = (np.arange(n, dtype=np.uint64) * np.uint64(2654435761) % np.uint64(1 << 32)).astype(np.uint32)
+    pa = bench.dump_outputs(str(tmp_path / "b"), big, 1, 0)
+    pb = bench.dump_outputs(str(tmp_path / "c"), big, 1, 0)
+    assert np.array_equal(np.load(pa), big[i1].astype(np.float64))
+    assert open(pa, "rb").read() == open(pb, "rb").read()
+
+
 def test_live_traffic_launch_selection():
     """bench.py's live-traffic reading (pick_launch_traffic): the big launches are
     chosen on FETCH_SIZE and the same launch positions are read from WRITE_SIZE, so a

@@ -51,7 +51,7 @@ for s in $STEPS; do
              run pmcmix2_$c 300 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE \
                  -d "$OUT/pmcmix2_$c" -o run --output-format csv -- python3 bench.py --config $c --steps 3 --warmup 1 --prewarm-s 0.3 --no-cpu-baseline --no-host-inclusive --no-live-traffic || exit 1
            done ;;
-    bench_c3) run bench_c3 600 python bench.py --config c3 --no-cpu-baseline --no-host-inclusive ;;
+    bench_c3) run bench_c3 600 python bench.py --full --config c3 --no-cpu-baseline --no-host-inclusive ;;
     tests_variant) # GPU parity of an A/B build: VARIANT=<abtest name>
            RPCCRC_LIB=$PWD/abtest/${VARIANT}.so run tests_variant_$VARIANT 600 python -u -m pytest tests/test_gpu_parity.py -m gpu -q -rfE \
                --timeout 120 --timeout-method thread -k "dynamic or stealing or c1_ or north_star or uniform or c2_ or c4_" ;;
@@ -88,15 +88,15 @@ for s in $STEPS; do
                    python3 tools/frames_lifted.py 3 ;;
     ragged) run ragged_${RAGGED_CFG:-c2} 300 python tools/probe.py --mode ragged --config ${RAGGED_CFG:-c2} --rounds ${RAGGED_ROUNDS:-3} --reps 5 ;;
     bench_scalar) run bench_scalar 300 tools/scalar_bench oracle/_ref/libref_crc.so ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     probe) run probe 600 python tools/probe.py ;;
     ablate) run ablate 600 python tools/probe.py --mode ablate --rounds 3 ;;
     ablate_nat) run ablate_nat 600 python tools/probe.py --mode ablate --rounds 3 --only $ABLATE ;;
     sustain) run sustain 600 python tools/probe.py --mode sustain --launches 1500 --smi-out $OUT/smi.jsonl --only $SUSTAIN ;;
     ablate_c1) run ablate_c1 600 python tools/probe.py --mode ablate --rounds 3 --config c1 --only qb4_pair1_nt1_abl0_d1,qb4_pair1_nt1_abl3_d1,qb4_pair1_nt1_abl4_d1,qb4_pair1_nt1_abl0_d2 ;;
-    bench_c1) run bench_c1 600 python bench.py --config c1 --no-cpu-baseline --no-host-inclusive ;;
-    bench_c2) run bench_c2 600 python bench.py --config c2 --no-cpu-baseline --no-host-inclusive ;;
-    bench_c2_rows) run bench_c2_rows 600 python bench.py --config c2 --ragged-path rows --no-cpu-baseline --no-host-inclusive --no-live-traffic ;;
+    bench_c1) run bench_c1 600 python bench.py --full --config c1 --no-cpu-baseline --no-host-inclusive ;;
+    bench_c2) run bench_c2 600 python bench.py --full --config c2 --no-cpu-baseline --no-host-inclusive ;;
+    bench_c2_rows) run bench_c2_rows 600 python bench.py --full --config c2 --ragged-path rows --no-cpu-baseline --no-host-inclusive --no-live-traffic ;;
     timeline) run timeline 300 python tools/probe.py --mode timeline --reps 3 ;;
     slowcap) # the slow mode: the lease's first processes, clocks read before and after
            rocm-smi --showclocks --showtemp --showpower > "$OUT/smi_before.txt" 2>&1
@@ -110,14 +110,14 @@ for s in $STEPS; do
            done ;;
     firstproc) # the lease's first processes: the same north-star line three times, then C3 twice
            for k in 1 2 3; do
-             run fp_ns_$k 300 python bench.py --no-cpu-baseline --no-host-inclusive --no-live-traffic --no-scalar-latency || exit 1
+             run fp_ns_$k 300 python bench.py --full --no-cpu-baseline --no-host-inclusive --no-live-traffic --no-scalar-latency || exit 1
            done
            for k in 1 2; do
-             run fp_c3_$k 300 python bench.py --config c3 --no-cpu-baseline --no-host-inclusive --no-live-traffic --no-scalar-latency || exit 1
+             run fp_c3_$k 300 python bench.py --full --config c3 --no-cpu-baseline --no-host-inclusive --no-live-traffic --no-scalar-latency || exit 1
            done ;;
     survey) # one box: every config's bench line (no PMC / CPU legs) and the steady-state NS clock
            for c in ns c1 c2 c3 c4; do
-             run survey_$c 300 python bench.py --config $c --no-cpu-baseline --no-host-inclusive --no-live-traffic --no-scalar-latency || exit 1
+             run survey_$c 300 python bench.py --full --config $c --no-cpu-baseline --no-host-inclusive --no-live-traffic --no-scalar-latency || exit 1
            done
            run survey_tl_ns 300 python tools/probe.py --mode timeline --reps 4 --config ns --steal --surround-ms 60 || exit 1 ;;
     slowss) # the shader clock in steady state: each timed launch inside 60 ms of back-to-back steps
@@ -160,7 +160,7 @@ for s in $STEPS; do
                python3 bench.py --config c4 --chunk-kib $k --steps 10 --warmup 3 --prewarm-s 0.2 --no-cpu-baseline --no-host-inclusive --no-live-traffic || exit 1
            done ;;
     packed) run packed 600 python tools/probe.py --mode packed --rounds 3 --reps 5 ;;
-    bench_c4) run bench_c4 600 python bench.py --config c4 --no-cpu-baseline --no-host-inclusive ;;
+    bench_c4) run bench_c4 600 python bench.py --full --config c4 --no-cpu-baseline --no-host-inclusive ;;
     counters) run counters 120 rocprofv3 -L ;;
     prof)  run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
                python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-host-inclusive --no-live-traffic ;;
