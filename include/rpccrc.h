@@ -110,6 +110,39 @@ RPCCRC_API int rpc_crc32_device_uniform(const uint8_t *d_base, uint64_t n, uint3
 RPCCRC_API int rpc_crc32_device_large(const uint8_t *d_base, const uint64_t *h_offsets, const uint64_t *h_lengths,
                            uint64_t n, uint32_t *d_out, uint64_t chunk_bytes, void *stream);
 
+/* ---- gathered and running CRCs ------------------------- */
+
+/* Gathered bodies.  Segment s = d_base[d_seg_offsets[s] .. + d_seg_lengths[s]).
+ * Body i is the concatenation, in order, of segments d_seg_first[i] ..
+ * d_seg_first[i+1]-1 (CSR: n+1 entries, non-decreasing, d_seg_first[0] == 0,
+ * d_seg_first[n] == nseg; this is the caller's contract, like the offsets).
+ * d_seed == NULL: d_out[i] = rpc_crc32 of the concatenation.
+ * d_seed != NULL: d_out[i] = zlib crc32(d_seed[i], concatenation), i.e.
+ *   rpc_crc32_combine(d_seed[i], rpc_crc32(concatenation), total length);
+ *   a body with no segments, or only empty ones, yields d_seed[i] (0 without seeds).
+ * max_seg_len: bound on the segment lengths, 0 = none (as _device_batch_bounded).
+ * A segment may belong to several bodies, segments may overlap and lie in any
+ * order in memory.  d_out may be the same pointer as d_seed.  Asynchronous.
+ * The segments are CRC'd as one rpc_crc32_device_batch (all its routes), then
+ * folded per body on the device with the GF(2) combine: a body's total length is
+ * 64-bit (it may exceed 4 GiB), and a body of many segments is folded by a whole
+ * workgroup.  n == 0: RPCCRC_OK, nothing touched.  nseg == 0 (d_base,
+ * d_seg_offsets, d_seg_lengths may then be NULL): every body is empty. */
+RPCCRC_API int rpc_crc32_device_gather(const uint8_t *d_base, const uint64_t *d_seg_offsets,
+                                       const uint32_t *d_seg_lengths, uint64_t nseg, uint32_t max_seg_len,
+                                       const uint64_t *d_seg_first, uint64_t n, const uint32_t *d_seed,
+                                       uint32_t *d_out, void *stream);
+
+/* The same over host memory; synchronous, staged as rpc_crc32_batch stages.  flags must be 0. */
+RPCCRC_API int rpc_crc32_batch_gather(const uint8_t *base, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                                      size_t nseg, const uint64_t *seg_first, size_t n, const uint32_t *seed,
+                                      uint32_t *out_crc, int flags);
+
+/* zlib's running form for one buffer: crc32(crc, data, len).  data == NULL -> 0
+ * (zlib returns 0 for Z_NULL whatever crc is); len reduced mod 2^32 as rpc_crc32.
+ * rpc_crc32 of the buffer (on the GPU, as the drop-in call) combined with crc. */
+RPCCRC_API uint32_t rpc_crc32_update(uint32_t crc, const void *data, size_t len);
+
 /* ---- frames (rpc.h:3-8 wire format) ------------------------------------ */
 
 /* Reference wire constants (rpc.h:11-18). */

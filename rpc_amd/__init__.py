@@ -30,9 +30,12 @@ __all__ = [
     "crc32_batch",
     "verify_batch",
     "crc32_combine",
+    "rpc_crc32_update",
+    "crc32_gather",
     "device_batch",
     "device_uniform",
     "device_large",
+    "device_gather",
     "frames_verify",
     "frames_stamp",
     "RxRing",
@@ -112,6 +115,16 @@ def rpc_crc32_verify(data, expected_crc: int, length: Optional[int] = None) -> b
     return bool(r)
 
 
+def rpc_crc32_update(crc: int, data, length: Optional[int] = None) -> int:
+    """zlib's running form crc32(crc, data, len); ``data`` None -> 0.  ``length`` defaults to len(data)."""
+    addr, n, keep = _as_buffer(data)
+    if length is None:
+        length = n
+    r = _lib.rpc_crc32_update(crc & 0xFFFFFFFF, addr, length)
+    del keep
+    return int(r)
+
+
 def crc32_combine(crc1: int, crc2: int, len2: int) -> int:
     """zlib crc32_combine semantics (zlib.h:1750)."""
     return int(_lib.rpc_crc32_combine(crc1 & 0xFFFFFFFF, crc2 & 0xFFFFFFFF, len2))
@@ -144,6 +157,31 @@ def verify_batch(buf, offsets, lengths, expected) -> tuple[int, np.ndarray]:
                                             off.shape[0], ok.ctypes.data), "rpc_crc32_verify_batch")
     del keep
     return int(bad), ok
+
+
+def crc32_gather(buf, seg_offsets: Sequence[int], seg_lengths: Sequence[int], seg_first: Sequence[int],
+                 seed: Optional[Sequence[int]] = None) -> np.ndarray:
+    """CRC of every body given as a segment list over host memory: body i is the
+    concatenation of ``buf[seg_offsets[s] : seg_offsets[s] + seg_lengths[s]]`` for
+    s = seg_first[i] .. seg_first[i+1]-1; with ``seed`` the bodies continue those running CRCs."""
+    addr, _, keep = _as_buffer(buf)
+    off = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+    ln = np.ascontiguousarray(seg_lengths, dtype=np.uint32)
+    first = np.ascontiguousarray(seg_first, dtype=np.uint64)
+    if off.shape != ln.shape:
+        raise ValueError("seg_offsets and seg_lengths differ in length")
+    if first.shape[0] < 1:
+        raise ValueError("seg_first needs n + 1 entries")
+    n = first.shape[0] - 1
+    sd = None if seed is None else np.ascontiguousarray(seed, dtype=np.uint32)
+    if sd is not None and sd.shape[0] != n:
+        raise ValueError("seed and seg_first differ in length")
+    out = np.empty(n, dtype=np.uint32)
+    check(_lib.rpc_crc32_batch_gather(addr, off.ctypes.data, ln.ctypes.data, off.shape[0], first.ctypes.data, n,
+                                      None if sd is None else sd.ctypes.data, out.ctypes.data, 0),
+          "rpc_crc32_batch_gather")
+    del keep
+    return out
 
 
 # ---- batched, device buffers (torch tensors as HBM plumbing) -----------------
@@ -207,6 +245,34 @@ def device_large(base, offsets: Iterable[int], lengths: Iterable[int], chunk: in
     out = _dev_u32_out(n, base.device, out)
     check(_lib.rpc_crc32_device_large(base.data_ptr(), off.ctypes.data, ln.ctypes.data, n, out.data_ptr(),
                                       chunk, _stream_handle(stream)), "rpc_crc32_device_large")
+    return out
+
+
+def device_gather(base, seg_offsets, seg_lengths, seg_first, seed=None, out=None, stream=None,
+                  max_seg_len: int = 0):
+    """Bodies given as segment lists over a device byte tensor (rpc_crc32_device_gather).
+
+    Segment s = base[seg_offsets[s] : + seg_lengths[s]]; body i is the concatenation of
+    segments seg_first[i] .. seg_first[i+1]-1 (CSR, int64/uint64 device tensor of n + 1
+    entries).  ``seed`` (4-byte device tensor, n entries): running CRCs the bodies continue
+    (zlib crc32(seed, body)); ``out`` may be the same tensor.  ``max_seg_len``: an upper
+    bound on the segment lengths (0 = none), as device_batch's ``max_len``.  With no
+    segments at all ``base``, ``seg_offsets`` and ``seg_lengths`` may be None."""
+    n = seg_first.numel() - 1
+    if n < 0:
+        raise ValueError("seg_first needs n + 1 entries")
+    nseg = 0 if seg_offsets is None else seg_offsets.numel()
+    if (0 if seg_lengths is None else seg_lengths.numel()) != nseg:
+        raise ValueError("seg_offsets and seg_lengths differ in length")
+    if nseg and base is None:
+        raise ValueError("segments need a base tensor")
+    if seed is not None and (seed.numel() < n or seed.element_size() != 4 or not seed.is_contiguous()):
+        raise ValueError("seed must be a contiguous 4-byte tensor with >= n elements")
+    out = _dev_u32_out(n, seg_first.device, out)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    check(_lib.rpc_crc32_device_gather(ptr(base), ptr(seg_offsets), ptr(seg_lengths), nseg,
+                                       int(max_seg_len) & 0xFFFFFFFF, seg_first.data_ptr(), n, ptr(seed),
+                                       out.data_ptr(), _stream_handle(stream)), "rpc_crc32_device_gather")
     return out
 
 

@@ -61,6 +61,9 @@ rpc_crc32_device_batch = _sig("rpc_crc32_device_batch", _i32, _vp, _vp, _vp, _u6
 rpc_crc32_device_batch_bounded = _sig("rpc_crc32_device_batch_bounded", _i32, _vp, _vp, _vp, _u64, _u32, _vp, _vp)
 rpc_crc32_device_uniform = _sig("rpc_crc32_device_uniform", _i32, _vp, _u64, _u32, _u64, _vp, _vp)
 rpc_crc32_device_large = _sig("rpc_crc32_device_large", _i32, _vp, _vp, _vp, _u64, _vp, _u64, _vp)
+rpc_crc32_device_gather = _sig("rpc_crc32_device_gather", _i32, _vp, _vp, _vp, _u64, _u32, _vp, _u64, _vp, _vp, _vp)
+rpc_crc32_batch_gather = _sig("rpc_crc32_batch_gather", _i32, _u8p, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i32)
+rpc_crc32_update = _sig("rpc_crc32_update", _u32, _u32, _vp, _sz)
 rpc_frames_verify_device = _sig("rpc_frames_verify_device", _i32, _vp, _u64, _vp, _u64, _i32, _vp, _vp, _vp)
 rpc_frames_stamp_device = _sig(
     "rpc_frames_stamp_device", _i32, _vp, _u64, _vp, _vp, _u64, ctypes.c_uint16, ctypes.c_uint16, _i32, _vp, _vp
@@ -101,6 +104,9 @@ EXPORTS = (
     "rpc_crc32_device_batch_bounded",
     "rpc_crc32_device_uniform",
     "rpc_crc32_device_large",
+    "rpc_crc32_device_gather",
+    "rpc_crc32_batch_gather",
+    "rpc_crc32_update",
     "rpc_frames_verify_device",
     "rpc_frames_stamp_device",
     "rpc_rx_ring_create",

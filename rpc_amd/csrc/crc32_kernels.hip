@@ -27,6 +27,7 @@
 #include "crc32_gf2.h"
 #include "crc32_kernels.h"
 #include "crc32_layout.h"
+#include "crc32_nib.h"
 #include "crc32_packed.h"
 #include "crc32_small.h"
 #include "crc32_rows.h"
@@ -40,25 +41,8 @@ namespace rpccrc {
 // k = 0..nch-1 (end-aligned chunks of `chunk` bytes, all crc0) are folded into
 // crc(body) = ~(A_L(F) ^ XOR_k A_{(nch-1-k)*chunk}(raw_k)).
 // ---------------------------------------------------------------------------
-// A_n(v) for n = sum of 2^k bytes, applied map by map from the nibble tables
-// NIB[k][i][j] = A_{2^k}(j << 4i) (64 maps x 8 nibble positions x 16, in LDS):
-// 8 lookups per set bit of n, instead of a bit-serial gf2_mulmod for x^(8n)
-// and another for the product (~30 of those per thread for C4's shifts).
-__device__ __forceinline__ uint32_t nib_apply(const uint32_t *nib, uint32_t k, uint32_t v) {
-  const uint32_t *m = nib + k * 128u;
-  uint32_t r = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 8; ++i) r ^= m[i * 16u + ((v >> (4u * i)) & 15u)];
-  return r;
-}
-__device__ __forceinline__ uint32_t nib_shift(const uint32_t *nib, uint64_t nbytes, uint32_t v) {
-  while (nbytes) {
-    const uint32_t k = (uint32_t)__builtin_ctzll(nbytes);
-    v = nib_apply(nib, k, v);
-    nbytes &= nbytes - 1;
-  }
-  return v;
-}
+// The shifts A_n are applied map by map from the nibble tables: nib_apply /
+// nib_shift, crc32_nib.h.
 
 // `splits` blocks per body; block s folds a contiguous run [c0, c1) of the
 // body's chunks.  Thread t takes chunks c0 + t, c0 + t + NT, ... (the raw

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/rpccrc.h"
+#include "crc32_gather.h"
 #include "crc32_gf2.h"
 #include "crc32_kernels.h"
 #include "crc32_layout.h"
@@ -1538,13 +1539,97 @@ int host_batch(DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, const
   return rc;
 }
 
+constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// ---- gathered bodies -----------------------------------------
+
+// Bodies given as segment lists: the ragged pass CRCs the nseg segments into a
+// leased workspace (every route of a ragged batch: rows, big bodies, dense
+// span), then the gather fold (crc32_gather.hip) combines them per body.
+// Stream-ordered, no host round trip.  The workspace is held until the fold is
+// enqueued.
+int device_gather(const DeviceCtx &c, const uint8_t *d_base, const uint64_t *d_seg_offsets,
+                  const uint32_t *d_seg_lengths, uint64_t nseg, uint32_t max_seg_len, const uint64_t *d_seg_first,
+                  uint64_t n, const uint32_t *d_seed, uint32_t *d_out, hipStream_t s) {
+  const size_t crc_bytes = align256(nseg * 4);
+  Lease ws;
+  if (const int rc = ws.get(c.ws, crc_bytes + gather_workspace_bytes(n, nseg), s)) return rc;
+  uint32_t *seg_crc = reinterpret_cast<uint32_t *>(ws.ptr());
+  if (nseg > 0) {
+    const bool route = max_seg_len == 0 || max_seg_len >= big_min_for(nseg); // as rpc_crc32_device_batch_bounded
+    if (const int rc = ragged(c, d_base, d_seg_offsets, d_seg_lengths, nseg, kModeFinal, seg_crc, s, false, route, nullptr, 0,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, max_seg_len))
+      return rc;
+  }
+  GatherArgs g{};
+  gather_carve(ws.ptr() + crc_bytes, n, nseg, &g);
+  g.seg_crc = seg_crc;
+  g.seg_len = d_seg_lengths;
+  g.seg_first = d_seg_first;
+  g.nseg = nseg;
+  g.n = n;
+  g.seed = d_seed;
+  g.out = d_out;
+  g.shift_nib = c.shift_nib;
+  return map_hip(launch_gather_fold(g, c.cus, s));
+}
+
+// The same over host memory: the segments are staged and CRC'd as
+// rpc_crc32_batch stages them, then the segment CRCs and the lists go to the
+// device for the fold.  Synchronous.
+int host_gather(DeviceCtx &c, const uint8_t *base, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                uint64_t nseg, const uint64_t *seg_first, uint64_t n, const uint32_t *seed, uint32_t *out) {
+  std::vector<uint32_t> seg_crc(nseg);
+  if (nseg > 0)
+    if (const int rc = host_batch(c, base, seg_offsets, seg_lengths, nseg, seg_crc.data())) return rc;
+  HostPipeline *p = c.pipes->acquire();
+  int rc = pipe_init(*p);
+  if (rc == RPCCRC_OK) {
+    hipStream_t s = p->slot[0].stream;
+    const size_t b_crc = align256(nseg * 4), b_len = align256(nseg * 4), b_first = align256((n + 1) * 8),
+                 b_io = align256(n * 4);
+    Lease ws;
+    rc = ws.get(c.ws, b_crc + b_len + b_first + b_io + gather_workspace_bytes(n, nseg), s);
+    auto run = [&]() -> int {
+      uint8_t *d = ws.ptr();
+      uint32_t *d_crc = reinterpret_cast<uint32_t *>(d);
+      uint32_t *d_len = reinterpret_cast<uint32_t *>(d + b_crc);
+      uint64_t *d_first = reinterpret_cast<uint64_t *>(d + b_crc + b_len);
+      uint32_t *d_io = reinterpret_cast<uint32_t *>(d + b_crc + b_len + b_first); // seeds in, CRCs out
+      if (nseg > 0) {
+        RPCCRC_TRY(hipMemcpyAsync(d_crc, seg_crc.data(), nseg * 4, hipMemcpyHostToDevice, s));
+        RPCCRC_TRY(hipMemcpyAsync(d_len, seg_lengths, nseg * 4, hipMemcpyHostToDevice, s));
+      }
+      RPCCRC_TRY(hipMemcpyAsync(d_first, seg_first, (n + 1) * 8, hipMemcpyHostToDevice, s));
+      if (seed) RPCCRC_TRY(hipMemcpyAsync(d_io, seed, n * 4, hipMemcpyHostToDevice, s));
+      GatherArgs g{};
+      gather_carve(d + b_crc + b_len + b_first + b_io, n, nseg, &g);
+      g.seg_crc = d_crc;
+      g.seg_len = d_len;
+      g.seg_first = d_first;
+      g.nseg = nseg;
+      g.n = n;
+      g.seed = seed ? d_io : nullptr;
+      g.out = d_io;
+      g.shift_nib = c.shift_nib;
+      RPCCRC_TRY(launch_gather_fold(g, c.cus, s));
+      RPCCRC_TRY(hipMemcpyAsync(out, d_io, n * 4, hipMemcpyDeviceToHost, s));
+      return RPCCRC_OK;
+    };
+    if (rc == RPCCRC_OK) rc = run();
+    // (the copies read and write the caller's memory: wait before returning, also after an error)
+    const hipError_t e = hipStreamSynchronize(s);
+    if (rc == RPCCRC_OK) rc = map_hip(e);
+  }
+  c.pipes->release(p);
+  return rc;
+}
+
 bool frames_flags_ok(int flags) {
   const int role = flags & (RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT);
   return (flags & ~(RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT | RPC_FRAMES_LIFT_CAP)) == 0 &&
          (role == RPC_FRAMES_SERVER || role == RPC_FRAMES_CLIENT);
 }
-
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 } // namespace
 } // namespace rpccrc
@@ -1638,6 +1723,38 @@ int rpc_crc32_device_large(const uint8_t *d_base, const uint64_t *h_offsets, con
   int rc = get_async_ctx(&c);
   if (rc) return rc;
   return device_large(*c, d_base, h_offsets, h_lengths, n, d_out, chunk_bytes, static_cast<hipStream_t>(stream));
+}
+
+int rpc_crc32_device_gather(const uint8_t *d_base, const uint64_t *d_seg_offsets, const uint32_t *d_seg_lengths,
+                            uint64_t nseg, uint32_t max_seg_len, const uint64_t *d_seg_first, uint64_t n,
+                            const uint32_t *d_seed, uint32_t *d_out, void *stream) {
+  if (n == 0) return RPCCRC_OK;
+  if (!d_seg_first || !d_out) return RPCCRC_EINVAL;
+  if (nseg > 0 && (!d_base || !d_seg_offsets || !d_seg_lengths)) return RPCCRC_EINVAL;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  return device_gather(*c, d_base, d_seg_offsets, d_seg_lengths, nseg, max_seg_len, d_seg_first, n, d_seed, d_out,
+                       static_cast<hipStream_t>(stream));
+}
+
+int rpc_crc32_batch_gather(const uint8_t *base, const uint64_t *seg_offsets, const uint32_t *seg_lengths, size_t nseg,
+                           const uint64_t *seg_first, size_t n, const uint32_t *seed, uint32_t *out_crc, int flags) {
+  if (flags != 0) return RPCCRC_EINVAL;
+  if (n == 0) return RPCCRC_OK;
+  if (!seg_first || !out_crc) return RPCCRC_EINVAL;
+  if (nseg > 0 && (!base || !seg_offsets || !seg_lengths)) return RPCCRC_EINVAL;
+  DeviceCtx *c = nullptr;
+  int rc = get_ctx(&c);
+  if (rc) return rc;
+  return host_gather(*c, base, seg_offsets, seg_lengths, nseg, seg_first, n, seed, out_crc);
+}
+
+uint32_t rpc_crc32_update(uint32_t crc, const void *data, size_t len) {
+  if (data == nullptr) return 0u; // zlib: Z_NULL -> 0 whatever crc is
+  const uint32_t len32 = (uint32_t)len;
+  if (len32 == 0) return crc;
+  return crc32_combine(crc, rpc_crc32(data, len32), len32);
 }
 
 int rpc_frames_verify_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_frame_offsets,
