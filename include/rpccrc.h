@@ -209,6 +209,71 @@ RPCCRC_API int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes,
                             const uint32_t *d_body_lens, uint64_t n, uint16_t version, uint16_t type, int flags,
                             uint8_t *d_verdict, void *stream);
 
+/* ---- frame scan: find the frames in raw connection bytes -----------------
+ * A connection is a byte run [d_conn_off[c], + d_conn_len[c]) of the device
+ * stream: what recv() has delivered so far, typically tens of pipelined frames
+ * and a partial one at the end.  Its frames are found by walking the headers
+ * from its first byte, with the reference's stop rules:
+ *   - fewer than 12 bytes left, or a body that is not complete yet: stop; the
+ *     partial frame is not emitted and not consumed (it is not here yet);
+ *   - a control frame (PING at a server, PONG at a client): 12 bytes, go on;
+ *   - body_len over MAX_BODY_LEN without LIFT_CAP (rpc_server_main.c:189-195),
+ *     or body_len 0 at a client (rpc_async.c:330-349): emitted (its verdict is
+ *     TOO_LARGE / RECV_ERR), 12 bytes consumed, the connection is CLOSED and
+ *     nothing behind it is looked at;
+ *   - otherwise a data frame of 12 + body_len bytes.
+ * Outputs (all device pointers; the call is asynchronous on `stream`):
+ *   d_frame_offsets[frame_cap]  absolute offsets in d_stream, grouped by
+ *       connection in connection order, stream order within a connection.
+ *       Only the first frame_cap frames are written, never anything at index
+ *       >= frame_cap; entries [*d_nframes, frame_cap) are set to stream_bytes,
+ *       which rpc_frames_verify_device calls MALFORMED with no body read, so
+ *       the array can go to verify with n = frame_cap and no host round trip.
+ *       NULL with frame_cap 0: count only (everything else is still written).
+ *   d_frame_conn[frame_cap]     the frame's connection (optional; 0xFFFFFFFF
+ *       in the padding entries)
+ *   d_conn_first[nconn + 1]     CSR over the frames found (also past frame_cap)
+ *   d_conn_consumed[nconn]      bytes of the connection the caller may drop;
+ *       the rest is the carry-over for the next recv()
+ *   d_conn_state[nconn]         RPC_CONN_OPEN / RPC_CONN_CLOSED
+ *   d_nframes[1]                frames found, also when > frame_cap
+ * A connection that does not lie inside the stream is CLOSED with no frames
+ * and nothing consumed.  nconn == 0 is RPCCRC_OK with *d_nframes = 0.  flags as
+ * rpc_frames_verify_device.  Every emitted frame is one rpc_frames_verify_device
+ * does not call MALFORMED. */
+#define RPC_FRAME_NOT_REACHED 6u /* fused call only: a frame behind one that closed its connection */
+#define RPC_CONN_OPEN 0u
+#define RPC_CONN_CLOSED 1u
+RPCCRC_API int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
+                           const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
+                           uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first, uint64_t *d_conn_consumed,
+                           uint8_t *d_conn_state, uint64_t *d_nframes, void *stream);
+
+/* Scan, then rpc_frames_verify_device on the frame_cap entries (d_verdict and
+ * d_crc hold frame_cap entries; d_crc may be NULL; padding entries read
+ * MALFORMED with crc 0), then within each connection every frame behind the
+ * first one whose verdict is BAD_CRC, TOO_LARGE or RECV_ERR becomes
+ * RPC_FRAME_NOT_REACHED with crc 0 -- the reference has closed the connection
+ * there (rpc_server_main.c:227-233) -- and a connection with a BAD_CRC becomes
+ * RPC_CONN_CLOSED.  d_conn_consumed keeps the scan's value. */
+RPCCRC_API int rpc_frames_scan_verify_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
+                           const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
+                           uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first, uint64_t *d_conn_consumed,
+                           uint8_t *d_conn_state, uint64_t *d_nframes, uint8_t *d_verdict, uint32_t *d_crc,
+                           void *stream);
+
+/* Route of the scan (results identical):
+ *   RPCCRC_SCAN_AUTO    connections longer than 96 KiB tiled, the rest serial
+ *   RPCCRC_SCAN_SERIAL  one lane per connection walks its headers
+ *   RPCCRC_SCAN_TILED   every connection of more than one 32 KiB tile is cut
+ *                       into tiles whose entry -> exit maps are composed
+ * Calls with RPC_FRAMES_LIFT_CAP always walk serially (the tiled route rests on
+ * frames of at most 12 + MAX_BODY_LEN bytes). */
+#define RPCCRC_SCAN_AUTO 0
+#define RPCCRC_SCAN_SERIAL 1
+#define RPCCRC_SCAN_TILED 2
+RPCCRC_API int rpc_frames_set_scan_path(int path);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

@@ -15,7 +15,7 @@ unless ``stream`` (a ``torch.cuda.Stream``) is given.
 from __future__ import annotations
 
 import ctypes
-from typing import Iterable, Optional, Sequence
+from typing import Iterable, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -38,6 +38,9 @@ __all__ = [
     "device_gather",
     "frames_verify",
     "frames_stamp",
+    "frames_scan",
+    "FrameScan",
+    "set_scan_path",
     "RxRing",
     "fill_random",
     "stream_read",
@@ -57,6 +60,9 @@ __all__ = [
     "FRAME_TOO_LARGE",
     "FRAME_MALFORMED",
     "FRAME_RECV_ERR",
+    "FRAME_NOT_REACHED",
+    "CONN_OPEN",
+    "CONN_CLOSED",
 ]
 
 # reference rpc.h:11-17
@@ -73,6 +79,9 @@ FRAME_CONTROL = 2
 FRAME_TOO_LARGE = 3
 FRAME_MALFORMED = 4
 FRAME_RECV_ERR = 5  # client role, body_len 0: rpc_async.c:330-349 drops the connection (RPC_RECV_ERR)
+FRAME_NOT_REACHED = 6  # frames_scan(verify=True): behind a frame that closed its connection
+CONN_OPEN = 0
+CONN_CLOSED = 1
 FRAMES_SERVER = 0x1
 FRAMES_CLIENT = 0x2
 FRAMES_LIFT_CAP = 0x4
@@ -316,6 +325,88 @@ def frames_stamp(stream_buf, frame_offsets, body_lens, version: int = 1, type_: 
                                        n, version, type_, FRAMES_LIFT_CAP if lift_cap else 0, verdict.data_ptr(),
                                        _stream_handle(stream)), "rpc_frames_stamp_device")
     return verdict
+
+
+class FrameScan(NamedTuple):
+    """What frames_scan returns (device tensors; ``nframes`` is the host-side count)."""
+    frame_offsets: object  # int64 [max_frames]: absolute offsets, padding entries = stream_bytes
+    frame_conn: object     # int32 [max_frames]: the frame's connection (-1 in the padding)
+    conn_first: object     # int64 [nconn + 1]: CSR over the frames found
+    consumed: object       # int64 [nconn]: bytes of each connection that may be dropped
+    state: object          # uint8 [nconn]: CONN_OPEN / CONN_CLOSED
+    verdict: object        # uint8 [max_frames] (verify=True), else None
+    crc: object            # int32 [max_frames] (verify=True), else None
+    nframes: int           # frames found
+
+
+def frames_scan(stream_buf, conn_offsets, conn_lengths, role: str = "server", lift_cap: bool = False,
+                max_frames: Optional[int] = None, verify: bool = False, stream=None, stream_bytes=None):
+    """Find the wire frames in raw connection bytes (rpc_frames_scan_device).
+
+    Connection c is ``stream_buf[conn_offsets[c] : + conn_lengths[c]]`` (int64/uint64 device
+    tensors).  Each connection's headers are walked from its first byte with the
+    reference's stop rules (include/rpccrc.h); a trailing partial frame is left for the
+    next read: ``consumed[c]`` bytes may be dropped, the rest is the carry-over.
+    ``max_frames=None`` counts first, synchronises once and allocates exactly; otherwise
+    the call raises if more than ``max_frames`` frames are found.  ``verify=True`` also
+    runs frames_verify on the frames found and marks what lies behind a closing frame
+    FRAME_NOT_REACHED (rpc_frames_scan_verify_device)."""
+    t = _torch()
+    dev = stream_buf.device
+    nconn = conn_offsets.numel()
+    if conn_lengths.numel() != nconn:
+        raise ValueError("conn_offsets and conn_lengths differ in length")
+    nbytes = stream_buf.numel() * stream_buf.element_size() if stream_bytes is None else int(stream_bytes)
+    flags = _frames_flags(role, lift_cap)
+    sh = _stream_handle(stream)
+    conn_first = t.empty(nconn + 1, dtype=t.int64, device=dev)
+    consumed = t.empty(nconn, dtype=t.int64, device=dev)
+    state = t.empty(nconn, dtype=t.uint8, device=dev)
+    nframes = t.empty(1, dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    def run(cap, offs, conn, verdict, crc):
+        common = (stream_buf.data_ptr(), nbytes, ptr(conn_offsets), ptr(conn_lengths), nconn, flags, ptr(offs),
+                  ptr(conn), cap, conn_first.data_ptr(), ptr(consumed), ptr(state), nframes.data_ptr())
+        if verdict is None:
+            check(_lib.rpc_frames_scan_device(*common, sh), "rpc_frames_scan_device")
+        else:
+            check(_lib.rpc_frames_scan_verify_device(*common, ptr(verdict), ptr(crc), sh),
+                  "rpc_frames_scan_verify_device")
+
+    def count():  # (the count is read on the call's stream: one synchronisation)
+        if stream is not None:
+            stream.synchronize()
+        return int(nframes.cpu()[0])
+
+    if max_frames is None:
+        run(0, None, None, None, None)
+        cap = count()
+    else:
+        cap = int(max_frames)
+    offs = t.empty(cap, dtype=t.int64, device=dev)
+    conn = t.empty(cap, dtype=t.int32, device=dev)
+    verdict = t.empty(cap, dtype=t.uint8, device=dev) if verify else None
+    crc = t.empty(cap, dtype=t.int32, device=dev) if verify else None
+    run(cap, offs, conn, verdict, crc)
+    found = count() if max_frames is not None else cap
+    if found > cap:
+        raise ValueError(f"frames_scan found {found} frames, max_frames is {cap}")
+    return FrameScan(offs, conn, conn_first, consumed, state, verdict, crc, found)
+
+
+#: rpc_frames_set_scan_path codes (include/rpccrc.h RPCCRC_SCAN_*)
+SCAN_PATHS = {"auto": 0, "serial": 1, "tiled": 2}
+
+
+def set_scan_path(path="auto"):
+    """Route of frames_scan (results identical): "auto" (long connections tiled, the rest
+    serial), "serial" (one lane per connection walks its headers) or "tiled" (every
+    cap-in-force connection of more than one tile takes the tile-map route)."""
+    code = SCAN_PATHS[path] if isinstance(path, str) else int(path)
+    check(_lib.rpc_frames_set_scan_path(code), "rpc_frames_set_scan_path")
 
 
 def fill_random(tensor, seed: int, stream=None):

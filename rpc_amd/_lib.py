@@ -68,6 +68,11 @@ rpc_frames_verify_device = _sig("rpc_frames_verify_device", _i32, _vp, _u64, _vp
 rpc_frames_stamp_device = _sig(
     "rpc_frames_stamp_device", _i32, _vp, _u64, _vp, _vp, _u64, ctypes.c_uint16, ctypes.c_uint16, _i32, _vp, _vp
 )
+rpc_frames_scan_device = _sig("rpc_frames_scan_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp, _u64, _vp, _vp, _vp,
+                              _vp, _vp)
+rpc_frames_scan_verify_device = _sig("rpc_frames_scan_verify_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp,
+                                     _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+rpc_frames_set_scan_path = _sig("rpc_frames_set_scan_path", _i32, _i32)
 rpc_rx_ring_create = _sig("rpc_rx_ring_create", _i32, ctypes.POINTER(ctypes.c_void_p), _sz, _sz, _i32, _i32)
 rpc_rx_ring_destroy = _sig("rpc_rx_ring_destroy", None, _vp)
 rpc_rx_ring_reserve = _sig("rpc_rx_ring_reserve", _i32, _vp, _sz, ctypes.POINTER(ctypes.c_void_p))
@@ -109,6 +114,9 @@ EXPORTS = (
     "rpc_crc32_update",
     "rpc_frames_verify_device",
     "rpc_frames_stamp_device",
+    "rpc_frames_scan_device",
+    "rpc_frames_scan_verify_device",
+    "rpc_frames_set_scan_path",
     "rpc_rx_ring_create",
     "rpc_rx_ring_destroy",
     "rpc_rx_ring_reserve",

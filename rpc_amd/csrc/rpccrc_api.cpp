@@ -35,6 +35,7 @@
 #include "crc32_layout.h"
 #include "crc32_service_math.h"
 #include "frames.h"
+#include "frames_scan.h"
 
 namespace rpccrc {
 namespace {
@@ -386,6 +387,7 @@ std::once_flag g_once[kMaxDevices];
 std::atomic<int> g_nontemporal{1}; // streamed once: non-temporal loads (measured faster)
 std::atomic<int> g_max_blocks{0};
 std::atomic<int> g_ragged_path{RPCCRC_RAGGED_AUTO};
+std::atomic<int> g_scan_path{RPCCRC_SCAN_AUTO};
 // Large-body chunk (rpc_crc32_device_large, chunk_bytes = 0).  C4 per call
 // (profiles/r01c4_*): 4 KiB 697 us (rows kernel fastest, combine 27 us),
 // 16 KiB 673 us, 64 KiB 689 us (each wave streams its own 64 KiB).
@@ -1636,6 +1638,118 @@ bool frames_flags_ok(int flags) {
 
 using namespace rpccrc;
 
+// rpc_frames_scan_device, and with d_verdict the fused scan + verify + reach pass.
+static int frames_scan_common(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
+                              const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
+                              uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first,
+                              uint64_t *d_conn_consumed, uint8_t *d_conn_state, uint64_t *d_nframes, uint8_t *d_verdict,
+                              uint32_t *d_crc, bool fused, void *stream) {
+  if (!frames_flags_ok(flags)) return RPCCRC_EINVAL;
+  if (!d_nframes || !d_conn_first || nconn >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (frame_cap != 0 && !d_frame_offsets) return RPCCRC_EINVAL;
+  if (nconn != 0 && (!d_stream || !d_conn_off || !d_conn_len || !d_conn_consumed || !d_conn_state))
+    return RPCCRC_EINVAL;
+  if (fused && frame_cap != 0 && (!d_verdict || !d_stream || frame_cap >= 0xFFFFFFFFull)) return RPCCRC_EINVAL;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool reach = fused && frame_cap != 0 && nconn != 0;
+
+  ScanArgs a;
+  a.stream = d_stream;
+  a.stream_bytes = stream_bytes;
+  a.conn_off = d_conn_off;
+  a.conn_len = d_conn_len;
+  a.nconn = nconn;
+  a.flags = flags;
+  a.frame_off = d_frame_offsets;
+  a.frame_conn = d_frame_conn;
+  a.frame_cap = frame_cap;
+  a.conn_first = d_conn_first;
+  a.consumed = d_conn_consumed;
+  a.state = d_conn_state;
+  a.nframes = d_nframes;
+
+  // The tiled route: cap in force only, for connections longer than tiled_min.
+  // Connections inside the stream that do not overlap need at most
+  // stream_bytes / T + (one more per tiled connection) tiles; what does not
+  // fit the workspace walks serially.
+  const int path = g_scan_path.load(std::memory_order_relaxed);
+  uint64_t tile_cap = 0;
+  a.tiled_min = path == RPCCRC_SCAN_TILED ? kScanTile : kScanTiledMin;
+  if (nconn != 0 && path != RPCCRC_SCAN_SERIAL && !(flags & RPC_FRAMES_LIFT_CAP) && stream_bytes > a.tiled_min) {
+    uint64_t max_tiles = 1;
+    for (uint32_t i = 0; i <= kScanMaxLevels; ++i) max_tiles *= kScanGroup;
+    tile_cap = stream_bytes / kScanTile + std::min<uint64_t>(nconn, stream_bytes / a.tiled_min) + 1;
+    tile_cap = std::min(tile_cap, max_tiles);
+  }
+  Lease tiled;
+  if (tile_cap) {
+    const int L = scan_levels_for(tile_cap);
+    size_t bytes = align256(nconn * 8) + align256((nconn + 1) * 8) + 256 + align256(tile_cap * 4) +
+                   align256(tile_cap * 8) + align256((tile_cap + 1) * 8);
+    for (int l = 0; l < L; ++l) {
+      const uint64_t nl = scan_level_count<kScanGroup>(tile_cap, (uint32_t)l);
+      bytes += align256(nl * kScanMapLen * 2) + align256(nl * 2);
+    }
+    if (tiled.get(c->ws, bytes, s) != RPCCRC_OK) {
+      tile_cap = 0; // no workspace: every connection walks serially (results identical)
+      (void)hipGetLastError(); // (the failed allocation's error is not the next launch's)
+    } else {
+      uint8_t *w = tiled.ptr();
+      auto take = [&w](size_t n) {
+        uint8_t *p = w;
+        w += align256(n);
+        return p;
+      };
+      a.levels = L;
+      a.conn_tiles = reinterpret_cast<uint64_t *>(take(nconn * 8));
+      a.tbase = reinterpret_cast<uint64_t *>(take((nconn + 1) * 8));
+      a.nt_live = reinterpret_cast<uint64_t *>(take(256));
+      a.tconn = reinterpret_cast<uint32_t *>(take(tile_cap * 4));
+      a.tile_cnt = reinterpret_cast<uint64_t *>(take(tile_cap * 8));
+      a.tpre = reinterpret_cast<uint64_t *>(take((tile_cap + 1) * 8));
+      for (int l = 0; l < L; ++l) {
+        const uint64_t nl = scan_level_count<kScanGroup>(tile_cap, (uint32_t)l);
+        a.maps[l] = reinterpret_cast<uint16_t *>(take(nl * kScanMapLen * 2));
+        a.entry[l] = reinterpret_cast<uint16_t *>(take(nl * 2));
+      }
+    }
+  }
+  a.tile_cap = tile_cap;
+
+  Lease base;
+  const size_t tmp_words = scan_tmp_words(std::max(nconn, tile_cap));
+  const bool own_conn = reach && !d_frame_conn;
+  const size_t base_bytes = align256(nconn * 8) + align256(tmp_words * 8) + (reach ? align256(nconn * 8) : 0) +
+                            (own_conn ? align256(frame_cap * 4) : 0);
+  uint64_t *first_close = nullptr;
+  {
+    // (nconn == 0 runs the same launches: no unit finds work, *d_nframes = 0,
+    // every entry of d_frame_offsets is padding)
+    if ((rc = base.get(c->ws, base_bytes + 256, s))) return rc;
+    uint8_t *w = base.ptr();
+    a.conn_cnt = reinterpret_cast<uint64_t *>(w);
+    w += align256(nconn * 8);
+    a.scan_tmp = reinterpret_cast<uint64_t *>(w);
+    w += align256(tmp_words * 8);
+    if (reach) {
+      first_close = reinterpret_cast<uint64_t *>(w);
+      w += align256(nconn * 8);
+    }
+    if (own_conn) a.frame_conn = reinterpret_cast<uint32_t *>(w);
+    if ((rc = map_hip(launch_frames_scan(a, s)))) return rc;
+  }
+  if (!fused || frame_cap == 0) return RPCCRC_OK;
+  if ((rc = rpc_frames_verify_device(d_stream, stream_bytes, d_frame_offsets, frame_cap, flags, d_verdict, d_crc,
+                                     stream)))
+    return rc;
+  if (!reach) return RPCCRC_OK;
+  return map_hip(launch_frames_reach(a.frame_conn, frame_cap, d_nframes, nconn, first_close, d_verdict, d_crc,
+                                     d_conn_state, s));
+}
+
 extern "C" {
 
 uint32_t rpc_crc32(const void *data, size_t len) {
@@ -1830,6 +1944,31 @@ int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes, const uint
     return rc;
   if (stamped) return RPCCRC_OK; // (route-all: the fold wrote the headers)
   return map_hip(launch_frames_stamp(st, bcrc, n, s));
+}
+
+int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
+                           const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
+                           uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first, uint64_t *d_conn_consumed,
+                           uint8_t *d_conn_state, uint64_t *d_nframes, void *stream) {
+  return frames_scan_common(d_stream, stream_bytes, d_conn_off, d_conn_len, nconn, flags, d_frame_offsets, d_frame_conn,
+                            frame_cap, d_conn_first, d_conn_consumed, d_conn_state, d_nframes, nullptr, nullptr, false,
+                            stream);
+}
+
+int rpc_frames_scan_verify_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
+                                  const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
+                                  uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first,
+                                  uint64_t *d_conn_consumed, uint8_t *d_conn_state, uint64_t *d_nframes,
+                                  uint8_t *d_verdict, uint32_t *d_crc, void *stream) {
+  return frames_scan_common(d_stream, stream_bytes, d_conn_off, d_conn_len, nconn, flags, d_frame_offsets, d_frame_conn,
+                            frame_cap, d_conn_first, d_conn_consumed, d_conn_state, d_nframes, d_verdict, d_crc, true,
+                            stream);
+}
+
+int rpc_frames_set_scan_path(int path) {
+  if (path != RPCCRC_SCAN_AUTO && path != RPCCRC_SCAN_SERIAL && path != RPCCRC_SCAN_TILED) return RPCCRC_EINVAL;
+  g_scan_path.store(path);
+  return RPCCRC_OK;
 }
 
 uint32_t rpc_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) { return crc32_combine(crc1, crc2, len2); }
