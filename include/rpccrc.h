@@ -209,6 +209,57 @@ RPCCRC_API int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes,
                             const uint32_t *d_body_lens, uint64_t n, uint16_t version, uint16_t type, int flags,
                             uint8_t *d_verdict, void *stream);
 
+/* ---- frame pack: build wire streams from bodies ---------------------------
+ * The mirror image of the scan.  Entry i is a type, a version and a body
+ * d_bodies[d_body_offsets[i], + d_body_lens[i]); the call computes the layout,
+ * copies the bodies into place, stamps the headers and leaves one contiguous
+ * byte run per connection to send().  For entry i, in this order:
+ *   1. t = d_types ? d_types[i] : type.  t == RPC_FRAME_TYPE_NONE: 0 bytes,
+ *      RPC_FRAME_SKIPPED; its offset and length are not looked at (the verdicts
+ *      of a scan can feed a reply batch with no compaction step).
+ *   2. t is PING or PONG: a heartbeat as the reference sends one
+ *      (conn_pool.c:248-257, rpc_server_main.c:172-187): 12 bytes, body_len 0,
+ *      crc32 0, RPC_FRAME_CONTROL; offset and length are not looked at.
+ *   3. Any other type is a data frame.  A body that does not lie inside
+ *      [0, bodies_bytes): RPC_FRAME_MALFORMED, 0 bytes.
+ *   4. len > RPC_MAX_BODY_LEN without RPC_FRAMES_LIFT_CAP: RPC_FRAME_TOO_LARGE,
+ *      0 bytes (rpc_async.c:499-501: the client does not send it).
+ *   5. Otherwise 12 + len bytes, RPC_FRAME_OK.
+ * Layout: d_frame_offsets[i] is the exclusive 64-bit sum of the sizes of
+ * entries 0 .. i-1, *d_total the sum of all; with a CSR d_conn_first[nconn + 1]
+ * over the entries (as the scan returns it) d_conn_bytes_first[c] is the frame
+ * offset of entry d_conn_first[c] and d_conn_bytes_first[nconn] is *d_total:
+ * connection c sends d_out[d_conn_bytes_first[c], d_conn_bytes_first[c + 1]).
+ * The layout never depends on out_cap.
+ * Capacity: an entry of non-zero size that does not end inside out_cap is not
+ * written, not even in part, and its verdict becomes RPC_FRAME_MALFORMED.
+ * Nothing at or beyond d_out + out_cap is written, and bytes of d_out that
+ * belong to no written frame are left untouched.  d_out == NULL with out_cap
+ * == 0 is the layout-only call: everything but d_out is written, so the caller
+ * can size the buffer from *d_total and call again.
+ * A written frame is its 12-byte big-endian header (rpc_async.c:521-530) and
+ * the body bytes.  d_crc[i]: the CRC stamped (bit-exact rpc_crc32), 0 for
+ * everything that is not a data frame of rule 5.  d_out must not overlap
+ * d_bodies.  Nothing outside [d_bodies, d_bodies + bodies_bytes) is read.
+ * All pointers are device pointers; d_frame_offsets, d_verdict, d_crc [n],
+ * d_conn_bytes_first [nconn + 1] and d_total [1] are optional; the call is
+ * asynchronous on `stream`.  flags: RPC_FRAMES_LIFT_CAP; role bits are accepted
+ * and ignored, as in stamp.
+ * RPCCRC_EINVAL, before any device is touched: unknown flag bits; n >=
+ * 0xFFFFFFFF; n > 0 with d_body_lens or d_body_offsets NULL (unless d_types is
+ * NULL and `type` is a heartbeat or NONE); bodies_bytes > 0 with d_bodies NULL;
+ * out_cap > 0 with d_out NULL; d_conn_bytes_first without d_conn_first; nconn >
+ * 0 with d_conn_first NULL.  n == 0 with neither d_total nor
+ * d_conn_bytes_first is RPCCRC_OK with no device; with them, *d_total and the
+ * nconn + 1 connection words are written as 0. */
+#define RPC_FRAME_SKIPPED 7u        /* pack only: the caller asked for no frame here */
+#define RPC_FRAME_TYPE_NONE 0xFFFFu /* pack only: type value meaning "emit nothing for this entry" */
+RPCCRC_API int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
+                           const uint32_t *d_body_lens, uint64_t n, const uint16_t *d_types, uint16_t type,
+                           const uint16_t *d_versions, uint16_t version, const uint64_t *d_conn_first, uint64_t nconn,
+                           int flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_frame_offsets, uint8_t *d_verdict,
+                           uint32_t *d_crc, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream);
+
 /* ---- frame scan: find the frames in raw connection bytes -----------------
  * A connection is a byte run [d_conn_off[c], + d_conn_len[c]) of the device
  * stream: what recv() has delivered so far, typically tens of pipelined frames

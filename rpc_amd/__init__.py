@@ -38,6 +38,8 @@ __all__ = [
     "device_gather",
     "frames_verify",
     "frames_stamp",
+    "frames_pack",
+    "FramePack",
     "frames_scan",
     "FrameScan",
     "set_scan_path",
@@ -61,6 +63,8 @@ __all__ = [
     "FRAME_MALFORMED",
     "FRAME_RECV_ERR",
     "FRAME_NOT_REACHED",
+    "FRAME_SKIPPED",
+    "TYPE_NONE",
     "CONN_OPEN",
     "CONN_CLOSED",
 ]
@@ -80,6 +84,8 @@ FRAME_TOO_LARGE = 3
 FRAME_MALFORMED = 4
 FRAME_RECV_ERR = 5  # client role, body_len 0: rpc_async.c:330-349 drops the connection (RPC_RECV_ERR)
 FRAME_NOT_REACHED = 6  # frames_scan(verify=True): behind a frame that closed its connection
+FRAME_SKIPPED = 7  # frames_pack: the caller asked for no frame here (TYPE_NONE)
+TYPE_NONE = 0xFFFF  # frames_pack: a type value meaning "emit nothing for this entry"
 CONN_OPEN = 0
 CONN_CLOSED = 1
 FRAMES_SERVER = 0x1
@@ -325,6 +331,84 @@ def frames_stamp(stream_buf, frame_offsets, body_lens, version: int = 1, type_: 
                                        n, version, type_, FRAMES_LIFT_CAP if lift_cap else 0, verdict.data_ptr(),
                                        _stream_handle(stream)), "rpc_frames_stamp_device")
     return verdict
+
+
+class FramePack(NamedTuple):
+    """What frames_pack returns (device tensors; ``total`` is the host-side byte count, or with
+    a caller's ``out`` -- nothing is read back then -- a one-element int64 device tensor)."""
+    stream: object            # uint8: the wire bytes; connection c is stream[conn_bytes_first[c] : conn_bytes_first[c + 1]]
+    offsets: object           # int64 [n]: where each entry's frame starts (entries of size 0 share the next one's)
+    verdict: object           # uint8 [n]: FRAME_OK / _CONTROL / _SKIPPED / _TOO_LARGE / _MALFORMED
+    crc: object               # int32 [n]: the CRC stamped (0 for everything that is no data frame)
+    conn_bytes_first: object  # int64 [nconn + 1], or None without conn_first
+    total: object             # bytes of all frames, whether they fitted or not
+
+
+def frames_pack(bodies, body_offsets, body_lens, types=None, version: int = 1, type_: int = RPC_TYPE_DATA,
+                versions=None, conn_first=None, lift_cap: bool = False, out=None, stream=None):
+    """Build wire streams from bodies (rpc_frames_pack_device): the mirror image of frames_scan.
+
+    Entry i is the body ``bodies[body_offsets[i] : + body_lens[i]]`` (uint8 device tensor;
+    int64/uint64 and int32/uint32 device tensors) with type ``types[i]`` and version
+    ``versions[i]`` (int16/uint16 device tensors), or ``type_`` / ``version`` for all.  A type
+    of TYPE_NONE emits nothing (FRAME_SKIPPED), PING / PONG a bare 12-byte heartbeat
+    (FRAME_CONTROL; offset and length are not looked at), anything else a data frame: header,
+    then the body.  ``conn_first`` (int64 [nconn + 1]) is a
+    CSR over the entries, as frames_scan returns it; connection c's bytes to send are
+    ``stream[conn_bytes_first[c] : conn_bytes_first[c + 1]]``.
+
+    ``out=None`` makes the layout-only call first, reads the total (one synchronisation, as
+    frames_scan does for its count), allocates exactly and packs.  With ``out`` (a contiguous
+    uint8 device tensor that does not overlap ``bodies``) nothing is read back: frames that do
+    not end inside it are FRAME_MALFORMED and not written, and ``total`` stays on the device."""
+    t = _torch()
+    if body_offsets is not None:
+        n = body_offsets.numel()
+    elif types is not None:
+        n = types.numel()
+    else:
+        raise ValueError("the number of entries comes from body_offsets or types")
+    for name, x, size in (("body_lens", body_lens, 4), ("types", types, 2), ("versions", versions, 2),
+                          ("body_offsets", body_offsets, 8)):
+        if x is not None and (x.numel() != n or x.element_size() != size or not x.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    if conn_first is not None and (conn_first.numel() < 1 or conn_first.element_size() != 8):
+        raise ValueError("conn_first needs nconn + 1 8-byte entries")
+    if out is not None and (out.element_size() != 1 or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 tensor")
+    dev = next(x for x in (bodies, body_offsets, types, out) if x is not None).device
+    nconn = 0 if conn_first is None else conn_first.numel() - 1
+    nbytes = 0 if bodies is None else bodies.numel() * bodies.element_size()
+    flags = FRAMES_LIFT_CAP if lift_cap else 0
+    sh = _stream_handle(stream)
+    offsets = t.empty(n, dtype=t.int64, device=dev)
+    verdict = t.empty(n, dtype=t.uint8, device=dev)
+    crc = t.empty(n, dtype=t.int32, device=dev)
+    cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
+    total = t.zeros(1, dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    def run(dst, layout_only):
+        check(_lib.rpc_frames_pack_device(ptr(bodies), nbytes if ptr(bodies) else 0, ptr(body_offsets), ptr(body_lens), n,
+                                          ptr(types), int(type_) & 0xFFFF, ptr(versions), int(version) & 0xFFFF,
+                                          None if conn_first is None else conn_first.data_ptr(), nconn, flags,
+                                          ptr(dst), 0 if dst is None else dst.numel(),
+                                          None if layout_only else ptr(offsets), None if layout_only else ptr(verdict),
+                                          None if layout_only else ptr(crc), None if layout_only else ptr(cbf),
+                                          total.data_ptr(), sh), "rpc_frames_pack_device")
+
+    if out is not None:
+        run(out, False)
+        return FramePack(out, offsets, verdict, crc, cbf, total)
+    run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
+    if stream is not None:
+        stream.synchronize()
+    nb = int(total.cpu()[0])
+    out = t.empty(nb, dtype=t.uint8, device=dev)
+    run(out, False)
+    return FramePack(out, offsets, verdict, crc, cbf, nb)
 
 
 class FrameScan(NamedTuple):

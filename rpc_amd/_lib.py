@@ -68,6 +68,8 @@ rpc_frames_verify_device = _sig("rpc_frames_verify_device", _i32, _vp, _u64, _vp
 rpc_frames_stamp_device = _sig(
     "rpc_frames_stamp_device", _i32, _vp, _u64, _vp, _vp, _u64, ctypes.c_uint16, ctypes.c_uint16, _i32, _vp, _vp
 )
+rpc_frames_pack_device = _sig("rpc_frames_pack_device", _i32, _vp, _u64, _vp, _vp, _u64, _vp, ctypes.c_uint16, _vp,
+                              ctypes.c_uint16, _vp, _u64, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_scan_device = _sig("rpc_frames_scan_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp, _u64, _vp, _vp, _vp,
                               _vp, _vp)
 rpc_frames_scan_verify_device = _sig("rpc_frames_scan_verify_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp,
@@ -114,6 +116,7 @@ EXPORTS = (
     "rpc_crc32_update",
     "rpc_frames_verify_device",
     "rpc_frames_stamp_device",
+    "rpc_frames_pack_device",
     "rpc_frames_scan_device",
     "rpc_frames_scan_verify_device",
     "rpc_frames_set_scan_path",

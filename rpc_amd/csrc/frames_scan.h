@@ -26,6 +26,8 @@
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+
+#include "excl_scan.h"
 #define SCAN_HD __host__ __device__ __forceinline__
 #else
 #define SCAN_HD inline
@@ -209,8 +211,7 @@ struct ScanArgs {
   uint16_t *maps[kScanMaxLevels + 1] = {};  // level l: ceil(tile_cap / G^l) maps
   uint16_t *entry[kScanMaxLevels + 2] = {}; // level l: as many resolved entries
 };
-// Words of scan_tmp an exclusive scan over n words needs.
-uint64_t scan_tmp_words(uint64_t n);
+// (scan_tmp_words(n), the words of scan_tmp a scan over n words needs: excl_scan.h)
 // Levels L for a workspace of tile_cap tiles (see ScanArgs::levels).
 int scan_levels_for(uint64_t tile_cap);
 // Enqueues the whole scan on s.

@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256) void scan_add_kernel(uint64_t *out, uint64_t n
   if (i < n) out[i] += chunk_base[i / kChunk];
   if (i == 0) out[n] = chunk_base[nb];
 }
+} // namespace
 
+// (declared in excl_scan.h: the frame pack scans its sizes with it too)
 hipError_t excl_scan(const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
   const uint64_t nb = (n + kChunk - 1) / kChunk;
   if (nb <= 1) {
@@ -80,6 +82,7 @@ hipError_t excl_scan(const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *tm
   return hipGetLastError();
 }
 
+namespace {
 // ---- the routes ---------------------------------------------------------------
 struct GlobalRd { // byte q of a connection, straight from global memory
   const uint8_t *b;

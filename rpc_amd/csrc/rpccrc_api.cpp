@@ -35,6 +35,7 @@
 #include "crc32_layout.h"
 #include "crc32_service_math.h"
 #include "frames.h"
+#include "frames_pack.h"
 #include "frames_scan.h"
 
 namespace rpccrc {
@@ -1944,6 +1945,82 @@ int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes, const uint
     return rc;
   if (stamped) return RPCCRC_OK; // (route-all: the fold wrote the headers)
   return map_hip(launch_frames_stamp(st, bcrc, n, s));
+}
+
+int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
+                           const uint32_t *d_body_lens, uint64_t n, const uint16_t *d_types, uint16_t type,
+                           const uint16_t *d_versions, uint16_t version, const uint64_t *d_conn_first, uint64_t nconn,
+                           int flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_frame_offsets, uint8_t *d_verdict,
+                           uint32_t *d_crc, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
+  if ((flags & ~(RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT | RPC_FRAMES_LIFT_CAP)) != 0) return RPCCRC_EINVAL;
+  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  const bool no_data = !d_types && !pack_is_data(type); // heartbeats or nothing: no body is looked at
+  if (n > 0 && !no_data && (!d_body_lens || !d_body_offsets)) return RPCCRC_EINVAL;
+  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
+  if (out_cap > 0 && !d_out) return RPCCRC_EINVAL;
+  if (d_conn_bytes_first && !d_conn_first) return RPCCRC_EINVAL;
+  if (nconn > 0 && !d_conn_first) return RPCCRC_EINVAL;
+  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) { // no entries: every offset is 0
+    if (d_total) RPCCRC_TRY(hipMemsetAsync(d_total, 0, 8, s));
+    if (d_conn_bytes_first) RPCCRC_TRY(hipMemsetAsync(d_conn_bytes_first, 0, (nconn + 1) * 8, s));
+    return RPCCRC_OK;
+  }
+  const size_t tmp_words = scan_tmp_words(n);
+  Lease wsl;
+  const size_t ws_bytes = 2 * align256(n * 8) + align256((n + 1) * 8) + align256(tmp_words * 8) +
+                          2 * align256(n * 4) + align256(n);
+  if ((rc = wsl.get(c->ws, ws_bytes, s))) return rc;
+  uint8_t *w = wsl.ptr();
+  auto take = [&w](size_t bytes) {
+    uint8_t *p = w;
+    w += align256(bytes);
+    return p;
+  };
+  PackArgs a;
+  a.bodies = d_bodies;
+  a.bodies_bytes = bodies_bytes;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.n = n;
+  a.types = d_types;
+  a.versions = d_versions;
+  a.type = type;
+  a.version = version;
+  a.conn_first = d_conn_first;
+  a.nconn = nconn;
+  a.flags = flags;
+  a.out = d_out;
+  a.out_cap = out_cap;
+  a.frame_off = d_frame_offsets;
+  a.verdict = d_verdict;
+  a.conn_bytes_first = d_conn_bytes_first;
+  a.total = d_total;
+  a.sizes = reinterpret_cast<uint64_t *>(take(n * 8));
+  a.src_off = reinterpret_cast<uint64_t *>(take(n * 8));
+  a.offs = reinterpret_cast<uint64_t *>(take((n + 1) * 8));
+  a.scan_tmp = reinterpret_cast<uint64_t *>(take(tmp_words * 8));
+  a.src_len = reinterpret_cast<uint32_t *>(take(n * 4));
+  uint32_t *own_crc = reinterpret_cast<uint32_t *>(take(n * 4));
+  a.crc = d_crc ? d_crc : own_crc;
+  a.pre = take(n);
+  if ((rc = map_hip(launch_frames_pack_layout(a, s)))) return rc;
+  // The CRCs, over the source bodies: the ragged call stamp makes (the length
+  // bound, the lifted-cap route), without its hooks.  A layout-only call that
+  // does not ask for them skips the pass; a batch that cannot hold a data
+  // frame has no body to read (every CRC is 0).
+  if (no_data || !d_bodies) { // (no source buffer: every body the CRC pass would read is empty)
+    RPCCRC_TRY(hipMemsetAsync(a.crc, 0, n * 4, s));
+  } else if (d_out || d_crc) {
+    const bool lift = (flags & RPC_FRAMES_LIFT_CAP) != 0;
+    if ((rc = ragged(*c, d_bodies, a.src_off, a.src_len, n, kModeFinal, a.crc, s, true, lift, nullptr, bodies_bytes)))
+      return rc;
+  }
+  return map_hip(launch_frames_pack_write(a, s));
 }
 
 int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
