@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "workspace.h"
+
 namespace rpccrc {
 
 // Bodies of at most this many segments are folded by one lane (64 consecutive
@@ -48,10 +50,9 @@ struct GatherArgs {
   uint64_t tile_cap;
 };
 
-// Workspace behind the segment CRCs: the counters, the worklists, the tile list.
-size_t gather_workspace_bytes(uint64_t n, uint64_t nseg);
-// Sets the counters, lists and capacities (the caller fills in the rest).
-void gather_carve(void *ws, uint64_t n, uint64_t nseg, GatherArgs *a);
+// Workspace behind the segment CRCs: the counters, the worklists, the tile
+// list.  Sets them and the capacities (the caller fills in the rest).
+void gather_layout(WsLayout &w, uint64_t n, uint64_t nseg, GatherArgs *a);
 // Zeroes the counters, then the lane kernel, the narrow fold, the tile pass and
 // the wide fold.  Stream-ordered; the launch shapes depend on n, nseg and cus only.
 hipError_t launch_gather_fold(const GatherArgs &a, int cus, hipStream_t s);

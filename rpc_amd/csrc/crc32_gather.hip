@@ -245,7 +245,6 @@ __global__ void __launch_bounds__(kGatherNarrowNT) gather_block_kernel(GatherArg
   }
 }
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 uint64_t cap_narrow(uint64_t n, uint64_t nseg) { return std::min<uint64_t>(n, nseg / (kGatherLaneMax + 1)); }
 uint64_t cap_wide(uint64_t n, uint64_t nseg) { return std::min<uint64_t>(n, nseg / kGatherWideMin); }
 // ceil(cnt / tile) summed over bodies with disjoint segment ranges
@@ -253,28 +252,17 @@ uint64_t cap_tiles(uint64_t n, uint64_t nseg) { return nseg / kGatherTile + cap_
 
 } // namespace
 
-size_t gather_workspace_bytes(uint64_t n, uint64_t nseg) {
-  return 256 + align256(cap_narrow(n, nseg) * 8) + 2 * align256(cap_wide(n, nseg) * 8) +
-         2 * align256(cap_tiles(n, nseg) * 8) + align256(cap_tiles(n, nseg) * 4);
-}
-
-void gather_carve(void *ws, uint64_t n, uint64_t nseg, GatherArgs *a) {
-  uint8_t *p = static_cast<uint8_t *>(ws);
-  auto take = [&p](size_t bytes) {
-    uint8_t *r = p;
-    p += align256(bytes);
-    return r;
-  };
-  a->work_n = reinterpret_cast<uint64_t *>(take(256));
+void gather_layout(WsLayout &w, uint64_t n, uint64_t nseg, GatherArgs *a) {
+  a->work_n = w.take<uint64_t>(32); // (a 256-byte line of its own)
   a->work_cap[0] = cap_narrow(n, nseg);
   a->work_cap[1] = cap_wide(n, nseg);
   a->tile_cap = cap_tiles(n, nseg);
-  a->work[0] = reinterpret_cast<uint64_t *>(take(a->work_cap[0] * 8));
-  a->work[1] = reinterpret_cast<uint64_t *>(take(a->work_cap[1] * 8));
-  a->wide_tile0 = reinterpret_cast<uint64_t *>(take(a->work_cap[1] * 8));
-  a->tile_slot = reinterpret_cast<uint64_t *>(take(a->tile_cap * 8));
-  a->tile_len = reinterpret_cast<uint64_t *>(take(a->tile_cap * 8));
-  a->tile_crc = reinterpret_cast<uint32_t *>(take(a->tile_cap * 4));
+  a->work[0] = w.take<uint64_t>(a->work_cap[0]);
+  a->work[1] = w.take<uint64_t>(a->work_cap[1]);
+  a->wide_tile0 = w.take<uint64_t>(a->work_cap[1]);
+  a->tile_slot = w.take<uint64_t>(a->tile_cap);
+  a->tile_len = w.take<uint64_t>(a->tile_cap);
+  a->tile_crc = w.take<uint32_t>(a->tile_cap);
 }
 
 hipError_t launch_gather_fold(const GatherArgs &a, int cus, hipStream_t s) {

@@ -3,11 +3,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "crc32_layout.h"
 #include "frames.h"
+#include "workspace.h"
 
 namespace rpccrc {
+
+// An on / off switch in the environment (callers read it once, into a static):
+// a default-on switch is off at NAME=0, a default-off one on at NAME=1.
+inline bool env_switch(const char *name, bool default_on) {
+  const char *e = getenv(name);
+  return default_on ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
 
 // Output modes of the items kernel.
 constexpr uint32_t kModeFinal = 0; // crc(M) = ~U(F, M)           (rpc_crc32 value)
@@ -119,8 +128,8 @@ struct DenseArgs {
   const uint32_t *tq; // Tq[q] = A_q(0xFFFFFFFF)
   const uint32_t *tab; // kDenseTabWords: the fold's maps (crc32_layout.h)
 };
-size_t dense_workspace_bytes(uint64_t n, uint64_t nb_cap);
-DenseArgs dense_carve(void *ws, uint64_t n, uint64_t nb_cap);
+// The workspace: sets n, nb_cap and the six arrays (the caller fills in the rest).
+void dense_layout(WsLayout &w, uint64_t n, uint64_t nb_cap, DenseArgs *d);
 inline uint64_t dense_plan_blocks(uint64_t n) { return (n + 1 + 255) / 256; } // 4 waves of 64 boundaries each
 // The plan (dense_plan_kernel) and the decision (dense_decide_kernel: DenseCtl).
 hipError_t launch_dense_plan(const DenseArgs &d, hipStream_t s);
@@ -203,9 +212,9 @@ struct BigRoute {
   const uint32_t *dbl = nullptr; // kBigDblWords: the fold's doubling maps per chunk class (build_big_dbl)
 };
 // (The fold's doubling maps per chunk class: crc32_layout.h build_big_dbl.)
-// span_rows: the span pass's block table (span mode, 0: off)
-size_t big_route_workspace_bytes(uint64_t n, uint64_t span_rows = 0);
-BigRoute big_route_carve(void *ws, uint64_t n, uint64_t span_rows = 0);
+// The workspace: sets the arrays (span_rows: the span pass's block table; span
+// mode, 0: off); the caller fills in the rest.
+void big_route_layout(WsLayout &w, uint64_t n, uint64_t span_rows, BigRoute *r);
 // Before the rows pass: flags and lists the big bodies (route.routed goes into
 // the rows pass's ItemsArgs).  Stream-ordered, no host round trip.
 // big_min: bodies of at least this many bytes are routed (kBigMin by default).
@@ -343,9 +352,9 @@ hipError_t launch_rows(const ItemsArgs &a, int QB, bool nt, int max_blocks, hipS
 hipError_t launch_chunk_combine(const CombineArgs &a, hipStream_t stream, hipEvent_t done = nullptr);
 
 // Packed ragged batches (crc32_packed.h): 1 KiB chunks of consecutive bodies,
-// four per row, balanced by chunk count; n < 2^32 - 1.  ws must hold
-// packed_workspace_bytes(n, max_slices) bytes of device memory, stream-ordered
-// with the launch (count, scan, plan and CRC kernels all run on `stream`).
+// four per row, balanced by chunk count; n < 2^32 - 1.  The workspace: device
+// memory laid out by packed_layout, stream-ordered with the launch (count, scan,
+// plan and CRC kernels all run on `stream`).
 struct PackedBatch {
   const uint8_t *base;
   const uint64_t *offsets;
@@ -355,25 +364,38 @@ struct PackedBatch {
   const uint4 *lds_image;
   const uint32_t *tq;
   uint32_t *out;
-  void *ws;
-  size_t ws_bytes;
   uint64_t max_slices; // slice-table capacity (balance granularity)
   uint64_t min_slice;  // chunks per slice, at least
+  uint32_t *cnt;       // workspace: n
+  uint64_t *cfirst;    // n
+  uint4 *slices;       // max_slices + 1
+  uint64_t *plan;      // [2]
+  void *scan;          // rocPRIM's scan scratch (scan_bytes of it), placed last
+  size_t scan_bytes;
 };
-hipError_t packed_workspace_bytes(uint64_t n, uint64_t max_slices, size_t *bytes);
+// The workspace of p->n bodies and p->max_slices slices (scan_bytes, here and
+// below: what *_scan_bytes(n) asks rocPRIM for, once per call).
+hipError_t packed_scan_bytes(uint64_t n, size_t *bytes);
+void packed_layout(WsLayout &w, size_t scan_bytes, PackedBatch *p);
 hipError_t launch_packed_batch(const PackedBatch &p, bool nt, int max_blocks, hipStream_t stream);
 // Split ragged batches (crc32_kernels.hip): small bodies (len + end pad <= 1 KiB)
 // through the QB = 4 rows kernel, the rest through QB = 1; n < 2^32 - 1.  proto
-// carries the batch (offsets / lengths required); ws must hold
-// split_workspace_bytes(n) bytes of device memory, stream-ordered with the launch.
+// carries the batch (offsets / lengths required); ws: device memory laid out by
+// split_layout, stream-ordered with the launch.
 struct SplitLists {
   uint64_t *counts; // [small, big]
   uint64_t *s_off, *b_off;
   uint32_t *s_len, *s_idx, *b_len, *b_idx;
 };
-hipError_t split_workspace_bytes(uint64_t n, size_t *bytes);
-hipError_t launch_split_batch(const ItemsArgs &proto, void *ws, size_t ws_bytes, bool nt, int max_blocks,
-                              hipStream_t stream);
+struct SplitWs {
+  uint32_t *pos; // n: the scan of the small flags
+  SplitLists l;  // n each
+  void *scan;    // rocPRIM's scan scratch, placed last
+  size_t scan_bytes;
+};
+hipError_t split_scan_bytes(uint64_t n, size_t *bytes);
+void split_layout(WsLayout &w, uint64_t n, size_t scan_bytes, SplitWs *ws);
+hipError_t launch_split_batch(const ItemsArgs &proto, const SplitWs &ws, bool nt, int max_blocks, hipStream_t stream);
 // Small bodies only (len + end pad <= 1 KiB each; crc32_small.h), CRC i to
 // out[out_idx[i]] (out_idx non-null) or out[i]; the count from *n_dev when set
 // (n_items: its upper bound).

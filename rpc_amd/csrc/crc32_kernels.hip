@@ -446,44 +446,36 @@ __global__ void __launch_bounds__(256) packed_plan_kernel(const uint64_t *cfirst
   for (uint64_t s = s_lo; s <= s_hi; ++s) slice_rec[s] = r;
 }
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 hipError_t packed_scan(void *tmp, size_t &bytes, const uint32_t *cnt, uint64_t *cfirst, uint64_t n, hipStream_t s) {
   return rocprim::exclusive_scan(tmp, bytes, cnt, cfirst, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
 }
 } // namespace
 
-hipError_t packed_workspace_bytes(uint64_t n, uint64_t max_slices, size_t *bytes) {
-  size_t scan = 0;
-  const hipError_t e = packed_scan(nullptr, scan, nullptr, nullptr, n, nullptr);
-  if (e != hipSuccess) return e;
-  *bytes = align256(n * 4) + align256(n * 8) + align256((max_slices + 1) * 16) + align256(16) + align256(scan);
-  return hipSuccess;
+hipError_t packed_scan_bytes(uint64_t n, size_t *bytes) {
+  return packed_scan(nullptr, *bytes, nullptr, nullptr, n, nullptr);
+}
+
+void packed_layout(WsLayout &w, size_t scan_bytes, PackedBatch *p) {
+  p->cnt = w.take<uint32_t>(p->n);
+  p->cfirst = w.take<uint64_t>(p->n);
+  p->slices = w.take<uint4>(p->max_slices + 1);
+  p->plan = w.take<uint64_t>(2);
+  p->scan = w.take<uint8_t>(scan_bytes);
+  p->scan_bytes = scan_bytes;
 }
 
 hipError_t launch_packed_batch(const PackedBatch &p, bool nt, int max_blocks, hipStream_t s) {
   if (p.n == 0) return hipSuccess;
   if (p.n >= 0xFFFFFFFFull || p.max_slices == 0 || p.min_slice == 0) return hipErrorInvalidValue;
-  uint8_t *w = static_cast<uint8_t *>(p.ws);
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(w);
-  w += align256(p.n * 4);
-  uint64_t *cfirst = reinterpret_cast<uint64_t *>(w);
-  w += align256(p.n * 8);
-  uint4 *slices = reinterpret_cast<uint4 *>(w);
-  w += align256((p.max_slices + 1) * 16);
-  uint64_t *plan = reinterpret_cast<uint64_t *>(w);
-  w += align256(16);
-  const size_t used = (size_t)(w - static_cast<uint8_t *>(p.ws));
-  if (used > p.ws_bytes) return hipErrorInvalidValue;
-  size_t scan = p.ws_bytes - used;
+  size_t scan = p.scan_bytes;
   hipLaunchKernelGGL(packed_count_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p.base, p.offsets,
-                     p.lengths, p.n, cnt, p.out);
+                     p.lengths, p.n, p.cnt, p.out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = packed_scan(w, scan, cnt, cfirst, p.n, s);
+  e = packed_scan(p.scan, scan, p.cnt, p.cfirst, p.n, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(packed_plan_kernel, dim3((unsigned)((p.n + 1 + 255) / 256)), dim3(256), 0, s, cfirst, cnt,
-                     p.offsets, p.lengths, p.n, p.max_slices, p.min_slice, slices, plan);
+  hipLaunchKernelGGL(packed_plan_kernel, dim3((unsigned)((p.n + 1 + 255) / 256)), dim3(256), 0, s, p.cfirst, p.cnt,
+                     p.offsets, p.lengths, p.n, p.max_slices, p.min_slice, p.slices, p.plan);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   PackedArgs a;
@@ -491,8 +483,8 @@ hipError_t launch_packed_batch(const PackedBatch &p, bool nt, int max_blocks, hi
   a.offsets = p.offsets;
   a.lengths = p.lengths;
   a.n_items = p.n;
-  a.slice_rec = slices;
-  a.plan = plan;
+  a.slice_rec = p.slices;
+  a.plan = p.plan;
   a.mode = p.mode;
   a.lds_image = p.lds_image;
   a.tq = p.tq;
@@ -575,10 +567,7 @@ hipError_t split_scan(void *tmp, size_t &bytes, const SmallFlag &f, uint32_t *po
 // The small-body kernel (crc32_small.h) for split lists; RPCCRC_SMALL_KERNEL=0
 // restores the rows kernel's QB = 4 loop (A/B).
 bool small_kernel_on() {
-  static const bool on = [] {
-    const char *e = getenv("RPCCRC_SMALL_KERNEL");
-    return e == nullptr || atoi(e) != 0;
-  }();
+  static const bool on = env_switch("RPCCRC_SMALL_KERNEL", true);
   return on;
 }
 
@@ -599,41 +588,34 @@ hipError_t launch_small(const ItemsArgs &a, bool nt, int max_blocks, hipStream_t
   return hipGetLastError();
 }
 
-hipError_t split_workspace_bytes(uint64_t n, size_t *bytes) {
-  size_t scan = 0;
-  const hipError_t e = split_scan(nullptr, scan, SmallFlag{}, nullptr, n, nullptr);
-  if (e != hipSuccess) return e;
-  *bytes = align256(n * 4) + align256(16) + 2 * (align256(n * 8) + 2 * align256(n * 4)) + align256(scan);
-  return hipSuccess;
+hipError_t split_scan_bytes(uint64_t n, size_t *bytes) {
+  return split_scan(nullptr, *bytes, SmallFlag{}, nullptr, n, nullptr);
 }
 
-hipError_t launch_split_batch(const ItemsArgs &proto, void *ws, size_t ws_bytes, bool nt, int max_blocks,
-                              hipStream_t s) {
+void split_layout(WsLayout &w, uint64_t n, size_t scan_bytes, SplitWs *ws) {
+  SplitLists &l = ws->l;
+  ws->pos = w.take<uint32_t>(n);
+  l.counts = w.take<uint64_t>(2);
+  l.s_off = w.take<uint64_t>(n);
+  l.s_len = w.take<uint32_t>(n);
+  l.s_idx = w.take<uint32_t>(n);
+  l.b_off = w.take<uint64_t>(n);
+  l.b_len = w.take<uint32_t>(n);
+  l.b_idx = w.take<uint32_t>(n);
+  ws->scan = w.take<uint8_t>(scan_bytes);
+  ws->scan_bytes = scan_bytes;
+}
+
+hipError_t launch_split_batch(const ItemsArgs &proto, const SplitWs &ws, bool nt, int max_blocks, hipStream_t s) {
   const uint64_t n = proto.n_items;
   if (n == 0) return hipSuccess;
   if (n > kMaxLaunchItems || proto.offsets == nullptr || proto.lengths == nullptr) return hipErrorInvalidValue;
-  uint8_t *w = static_cast<uint8_t *>(ws);
-  auto take = [&](size_t bytes) {
-    uint8_t *r = w;
-    w += align256(bytes);
-    return r;
-  };
-  uint32_t *pos = reinterpret_cast<uint32_t *>(take(n * 4));
-  SplitLists l;
-  l.counts = reinterpret_cast<uint64_t *>(take(16));
-  l.s_off = reinterpret_cast<uint64_t *>(take(n * 8));
-  l.s_len = reinterpret_cast<uint32_t *>(take(n * 4));
-  l.s_idx = reinterpret_cast<uint32_t *>(take(n * 4));
-  l.b_off = reinterpret_cast<uint64_t *>(take(n * 8));
-  l.b_len = reinterpret_cast<uint32_t *>(take(n * 4));
-  l.b_idx = reinterpret_cast<uint32_t *>(take(n * 4));
-  const size_t used = (size_t)(w - static_cast<uint8_t *>(ws));
-  if (used > ws_bytes) return hipErrorInvalidValue;
-  size_t scan = ws_bytes - used;
+  const SplitLists &l = ws.l;
+  size_t scan = ws.scan_bytes;
   const dim3 g((unsigned)((n + 255) / 256));
-  hipError_t e = split_scan(w, scan, SmallFlag{proto.base, proto.offsets, proto.lengths}, pos, n, s);
+  hipError_t e = split_scan(ws.scan, scan, SmallFlag{proto.base, proto.offsets, proto.lengths}, ws.pos, n, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(split_scatter_kernel, g, dim3(256), 0, s, proto.base, proto.offsets, proto.lengths, n, pos, l);
+  hipLaunchKernelGGL(split_scatter_kernel, g, dim3(256), 0, s, proto.base, proto.offsets, proto.lengths, n, ws.pos, l);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   ItemsArgs a = proto; // small bodies, four per row
@@ -1226,33 +1208,19 @@ __global__ void __launch_bounds__(kFoldThreads) big_combine_aligned_kernel(const
 
 } // namespace
 
-size_t big_route_workspace_bytes(uint64_t n, uint64_t span_rows) {
-  return align256((n + 63) / 64 * 8) + align256(64) + align256(kBigMaxBodies * 4) +
-         align256((kBigMaxBodies + 1) * 8) + align256(kBigMaxChunks * 8) + 2 * align256(kBigMaxChunks * 4) +
-         (span_rows ? align256((span_rows + 1) * 4) + align256((span_rows / 32 + 1) * 4) : 0);
-}
-
-BigRoute big_route_carve(void *ws, uint64_t n, uint64_t span_rows) {
-  uint8_t *w = static_cast<uint8_t *>(ws);
-  auto take = [&](size_t bytes) {
-    uint8_t *p = w;
-    w += align256(bytes);
-    return p;
-  };
-  BigRoute r;
-  r.routed = reinterpret_cast<uint32_t *>(take((n + 63) / 64 * 8));
-  r.meta = reinterpret_cast<uint64_t *>(take(64));
-  r.b_idx = reinterpret_cast<uint32_t *>(take(kBigMaxBodies * 4));
-  r.b_first = reinterpret_cast<uint64_t *>(take((kBigMaxBodies + 1) * 8));
-  r.c_off = reinterpret_cast<uint64_t *>(take(kBigMaxChunks * 8));
-  r.c_len = reinterpret_cast<uint32_t *>(take(kBigMaxChunks * 4));
-  r.c_raw = reinterpret_cast<uint32_t *>(take(kBigMaxChunks * 4));
+void big_route_layout(WsLayout &w, uint64_t n, uint64_t span_rows, BigRoute *r) {
+  r->routed = w.take<uint32_t>((n + 63) / 64 * 2);
+  r->meta = w.take<uint64_t>(8);
+  r->b_idx = w.take<uint32_t>(kBigMaxBodies);
+  r->b_first = w.take<uint64_t>(kBigMaxBodies + 1);
+  r->c_off = w.take<uint64_t>(kBigMaxChunks);
+  r->c_len = w.take<uint32_t>(kBigMaxChunks);
+  r->c_raw = w.take<uint32_t>(kBigMaxChunks);
   if (span_rows) {
-    r.blk = reinterpret_cast<uint32_t *>(take((span_rows + 1) * 4)); // (+1: the fold's idle loads read blk[j0])
-    r.rnd = reinterpret_cast<uint32_t *>(take((span_rows / 32 + 1) * 4)); // (the host clears it when unused)
-    r.span_rows_max = span_rows;
+    r->blk = w.take<uint32_t>(span_rows + 1); // (+1: the fold's idle loads read blk[j0])
+    r->rnd = w.take<uint32_t>(span_rows / 32 + 1); // (the host clears it when unused)
+    r->span_rows_max = span_rows;
   }
-  return r;
 }
 
 hipError_t launch_big_classify(const uint32_t *lengths, uint64_t n, uint32_t big_min, const BigRoute &r,
@@ -1415,28 +1383,15 @@ hipError_t launch_stream_read(const void *p, uint64_t nbytes, int pattern, bool 
 
 // ---- dense span mode (tests/test_dense_emu.py restates it) ----
 
-size_t dense_workspace_bytes(uint64_t n, uint64_t nb_cap) {
-  return align256(sizeof(DenseCtl)) + align256(nb_cap * 16) + align256((n + 1) * 2) + align256((n + 1) * 8) +
-         align256(nb_cap * 4) + align256(dense_plan_blocks(n) * 4);
-}
-
-DenseArgs dense_carve(void *ws, uint64_t n, uint64_t nb_cap) {
-  uint8_t *w = static_cast<uint8_t *>(ws);
-  auto take = [&](size_t bytes) {
-    uint8_t *p = w;
-    w += align256(bytes);
-    return p;
-  };
-  DenseArgs d{};
-  d.n = n;
-  d.nb_cap = nb_cap;
-  d.ctl = reinterpret_cast<DenseCtl *>(take(sizeof(DenseCtl)));
-  d.rec = reinterpret_cast<uint4 *>(take(nb_cap * 16));
-  d.bpos = reinterpret_cast<uint16_t *>(take((n + 1) * 2));
-  d.bnd = reinterpret_cast<uint2 *>(take((n + 1) * 8));
-  d.W = reinterpret_cast<uint32_t *>(take(nb_cap * 4));
-  d.flags = reinterpret_cast<uint32_t *>(take(dense_plan_blocks(n) * 4));
-  return d;
+void dense_layout(WsLayout &w, uint64_t n, uint64_t nb_cap, DenseArgs *d) {
+  d->n = n;
+  d->nb_cap = nb_cap;
+  d->ctl = w.take<DenseCtl>(1);
+  d->rec = w.take<uint4>(nb_cap);
+  d->bpos = w.take<uint16_t>(n + 1);
+  d->bnd = w.take<uint2>(n + 1);
+  d->W = w.take<uint32_t>(nb_cap);
+  d->flags = w.take<uint32_t>(dense_plan_blocks(n));
 }
 
 namespace {

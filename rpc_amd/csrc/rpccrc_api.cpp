@@ -173,6 +173,17 @@ struct Lease {
     return p->acquire(bytes, stream, &b);
   }
   uint8_t *ptr() const { return static_cast<uint8_t *>(b.p); }
+  // A block for the arrays that layout(WsLayout &) takes, and slack bytes behind
+  // them: a measuring pass sizes the lease, the same function then carves it.
+  template <class F> int get(BlockPool *p, hipStream_t stream, F &&layout, size_t slack = 0) {
+    WsLayout m;
+    layout(m);
+    if (!m.ok()) return RPCCRC_EINVAL;
+    if (const int rc = get(p, m.used() + slack, stream)) return rc;
+    WsLayout w(ptr(), m.used());
+    layout(w);
+    return w.ok() ? RPCCRC_OK : RPCCRC_EINVAL;
+  }
 };
 
 // Two-word device counters for the rows kernel's tail stealing (crc32_rows.h
@@ -421,10 +432,7 @@ uint32_t big_min_for(uint64_t n) {
 // chunks of rounds 2-3).  The plan doubles the size until the chunks fit
 // kBigMaxChunks.  Tuning override: RPCCRC_BIG_CHUNK (bytes: a power of two
 // >= 4096 aligned, 2^k * 4096 - 16 end-aligned).
-const bool g_big_aligned = [] {
-  const char *e = getenv("RPCCRC_BIG_ALIGNED");
-  return !(e && e[0] == '0');
-}();
+const bool g_big_aligned = env_switch("RPCCRC_BIG_ALIGNED", true);
 const uint64_t g_big_chunk = [] {
   const char *e = getenv("RPCCRC_BIG_CHUNK");
   const unsigned long long v = e ? strtoull(e, nullptr, 10) : 0ull;
@@ -437,17 +445,11 @@ constexpr uint64_t kSplitMinFrames = 16384;       // fewer frames: one wave per 
 constexpr uint64_t kRouteAllMax = 2048;           // lifted-cap frames batches up to this size: route-all
 // Route-all span mode (BigRoute): on by default; RPCCRC_BIG_SPAN=0
 // keeps every body on the chunk route.  Streams below kSpanMinBytes keep it too.
-const bool g_big_span = [] {
-  const char *e = getenv("RPCCRC_BIG_SPAN");
-  return !(e && e[0] == '0');
-}();
+const bool g_big_span = env_switch("RPCCRC_BIG_SPAN", true);
 constexpr uint64_t kSpanMinBytes = 1ull << 20;
 // Round values for one-row chunks of contiguous large bodies (device_large):
 // on by default; RPCCRC_ROUND_COMBINE=0 folds the per-chunk CRCs.
-const bool g_round_combine = [] {
-  const char *e = getenv("RPCCRC_ROUND_COMBINE");
-  return !(e && e[0] == '0');
-}();
+const bool g_round_combine = env_switch("RPCCRC_ROUND_COMBINE", true);
 constexpr bool kAutoSplitFrames = true;           // AUTO frames batches: split (true) or packed (false)
 constexpr uint64_t kPackedMaxSlices = 1ull << 21; // slice-table cap (8 MiB)
 // Chunks per packed slice, at least: a slice switch costs the wave two scalar
@@ -565,16 +567,19 @@ int get_async_ctx(DeviceCtx **out) {
   return rc ? rc : device_error(**out);
 }
 
+#ifdef RPCCRC_TEST_HOOKS
+long env_count(const char *name) { // NAME=K: a test hook's budget of K uses
+  const char *e = getenv(name);
+  return e ? atol(e) : 0L;
+}
+#endif
 // Test hook, compiled into the test build only (librpccrc_test.so,
 // -DRPCCRC_TEST_HOOKS; ADVICE r03: the shipping library must not read it):
 // RPCCRC_TEST_STEAL_GIVEUP=K makes the next K tail-stealing launches give up
 // every pool-round wait (ItemsArgs.test_giveup), to exercise the error words.
 uint32_t take_test_giveup() {
 #ifdef RPCCRC_TEST_HOOKS
-  static std::atomic<long> left{[] {
-    const char *e = getenv("RPCCRC_TEST_STEAL_GIVEUP");
-    return e ? atol(e) : 0L;
-  }()};
+  static std::atomic<long> left{env_count("RPCCRC_TEST_STEAL_GIVEUP")};
   return left.fetch_sub(1) > 0 ? 1u : 0u;
 #else
   return 0u;
@@ -588,10 +593,7 @@ uint32_t take_test_giveup() {
 // (tests/test_gpu_parity.py test_dense_mode_covers_every_crc).
 bool test_dense_only() {
 #ifdef RPCCRC_TEST_HOOKS
-  static const bool v = [] {
-    const char *e = getenv("RPCCRC_TEST_DENSE_ONLY");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env_switch("RPCCRC_TEST_DENSE_ONLY", false);
   return v;
 #else
   return false;
@@ -638,10 +640,7 @@ ItemsArgs items_args(const DeviceCtx &c, const uint8_t *base, const uint64_t *of
 // per-step events, profiles/r02/r02aj_step_events_ab.txt).
 // RPCCRC_STEAL_EXT_EVENT=0 records it separately (A/B only).
 bool steal_ext_event() {
-  static const bool v = [] {
-    const char *e = getenv("RPCCRC_STEAL_EXT_EVENT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_switch("RPCCRC_STEAL_EXT_EVENT", true);
   return v;
 }
 struct StealLease {
@@ -656,14 +655,18 @@ struct StealLease {
   ~StealLease() {
     if (pool) pool->release(slot, s, recorded, !steal_ext_event());
   }
-  int get(const DeviceCtx &c, uint64_t n, int QB, hipStream_t stream) {
-    const uint64_t tasks = QB == 4 ? (n + 3) / 4 : n;
-    if (tasks < 8ull * dyn_round(QB) * (uint64_t)max_blocks_for(c)) return RPCCRC_OK; // launch_rows: not DYN
+  int acquire(const DeviceCtx &c, hipStream_t stream) {
     if (const int rc = c.steal->acquire(stream, &slot)) return rc;
     p = slot->p;
     pool = c.steal;
     s = stream;
     return RPCCRC_OK;
+  }
+  // ... for a rows launch of n items, when it deals dynamically
+  int get(const DeviceCtx &c, uint64_t n, int QB, hipStream_t stream) {
+    const uint64_t tasks = QB == 4 ? (n + 3) / 4 : n;
+    if (tasks < 8ull * dyn_round(QB) * (uint64_t)max_blocks_for(c)) return RPCCRC_OK; // launch_rows: not DYN
+    return acquire(c, stream);
   }
   hipEvent_t done_event() const { return steal_ext_event() && slot ? slot->ev : nullptr; }
 };
@@ -674,20 +677,14 @@ struct StealLease {
 // the one loop made every row dearer and stealing cost C2 +0.7 % (round 2),
 // +2.3 % (round 3), +1.8 % (round 5, r05w).  RPCCRC_RAGGED_STEAL=0 turns it off.
 bool ragged_steal() {
-  static const bool v = [] {
-    const char *e = getenv("RPCCRC_RAGGED_STEAL");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_switch("RPCCRC_RAGGED_STEAL", true);
   return v;
 }
 
 // Dense span mode for ragged device batches.  RPCCRC_DENSE=0
 // turns it off (the rows pass only, as in rounds 1-5).
 bool dense_enabled() {
-  static const bool v = [] {
-    const char *e = getenv("RPCCRC_DENSE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_switch("RPCCRC_DENSE", true);
   return v;
 }
 
@@ -717,17 +714,32 @@ int items(const DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, cons
 //  * span_bytes (frames calls: the stream length; 0 otherwise): a route-all
 //    batch over a 4 KiB-aligned base may take the route's span mode (BigRoute).
 //  * cmp (frames verify): in route-all mode the fold writes the verdicts too
-//    and *compared is set (the caller then skips its compare launch).
+//    and compared is set (the caller then skips its compare launch).
 struct FramesCmp {
   const uint32_t *expected;
   const uint8_t *pre;
   uint8_t *verdict;
 };
-int ragged(const DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, const uint32_t *lengths, uint64_t n,
-           uint32_t mode, uint32_t *out, hipStream_t s, bool small_bodies, bool route, uint32_t *err = nullptr,
-           uint64_t span_bytes = 0, const FramesCmp *cmp = nullptr, bool *compared = nullptr,
-           const FramesParse *fparse = nullptr, const FramesStamp *fstamp = nullptr, bool *stamped = nullptr,
-           uint32_t max_len = 0) {
+struct RaggedCall {
+  const uint8_t *base; // the batch
+  const uint64_t *offsets;
+  const uint32_t *lengths;
+  uint64_t n;
+  uint32_t *out;
+  uint32_t mode = kModeFinal;
+  bool small_bodies = false; // hints
+  bool route = false;
+  uint32_t max_len = 0; // the caller's bound on every length (0: none)
+  uint64_t span_bytes = 0;
+  uint32_t *err = nullptr; // the launches' error word (as items())
+  const FramesCmp *cmp = nullptr; // frames hooks
+  const FramesParse *parse = nullptr;
+  const FramesStamp *stamp = nullptr;
+  bool compared = false; // results
+  bool stamped = false;
+};
+int ragged(const DeviceCtx &c, RaggedCall &q, hipStream_t s) {
+  const uint64_t n = q.n;
   const int path = g_ragged_path.load(std::memory_order_relaxed);
   const bool nt = nontemporal();
   const int mb = max_blocks_for(c);
@@ -736,63 +748,65 @@ int ragged(const DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, con
   // scan / scatter passes and second rows launch cost ~20 us, which only a
   // batch of many frames repays (1M frames: 334 vs 565 us); a
   // small batch (e.g. 1024 lifted-cap frames) takes the rows kernel directly.
-  const bool auto_frames = path == RPCCRC_RAGGED_AUTO && small_bodies && n >= kSplitMinFrames;
+  const bool auto_frames = path == RPCCRC_RAGGED_AUTO && q.small_bodies && n >= kSplitMinFrames;
   const bool packed = fits && (path == RPCCRC_RAGGED_PACKED || (auto_frames && !kAutoSplitFrames));
   const bool split = !packed && n <= kMaxLaunchItems && (path == RPCCRC_RAGGED_SPLIT || (auto_frames && kAutoSplitFrames));
-  route = route && !packed && mode == kModeFinal && n <= kMaxLaunchItems;
+  const bool route = q.route && !packed && q.mode == kModeFinal && n <= kMaxLaunchItems;
   // Route-all: a lifted-cap frames batch of at most kRouteAllMax frames sends
   // every body through the chunk route (no classify pass and no plain rows
   // pass, whose longest non-routed body -- up to the 16 KiB small-batch
   // threshold, one wave -- set its duration: 15 us of a 1024-frame verify).
   // Bounded because the fold spends a block-wide reduction per body (1024
   // blocks): a few bodies per block cost less than the passes they replace.
-  const bool route_all = route && small_bodies && !split && n <= kRouteAllMax && !g_big_min_env;
-  // fparse (frames verify): the route-all aligned plan parses the headers
+  const bool route_all = route && q.small_bodies && !split && n <= kRouteAllMax && !g_big_min_env;
+  // parse (frames verify): the route-all aligned plan parses the headers
   // itself; any other path needs them parsed before its first launch.
-  const bool fuse_parse = fparse && route_all && g_big_aligned;
-  if (fparse && !fuse_parse)
-    RPCCRC_TRY(launch_frames_parse(fparse->stream, fparse->stream_bytes, fparse->frame_off, n, fparse->flags,
-                                   fparse->body_off, fparse->body_len, fparse->hdr_crc, fparse->pre, s));
-  // fstamp (frames stamp): likewise the stamp's bounds / cap check, and the fold
-  // then writes the headers (*stamped set; the caller skips its stamp launch).
-  const bool fuse_stamp = fstamp && route_all && g_big_aligned;
-  if (fstamp && !fuse_stamp) RPCCRC_TRY(launch_frames_stamp_prep(*fstamp, n, s));
-  ItemsArgs a = items_args(c, base, offsets, lengths, n, 0, 0, mode, out);
-  if (err) a.err = err;
+  const bool fuse_parse = q.parse && route_all && g_big_aligned;
+  if (q.parse && !fuse_parse)
+    RPCCRC_TRY(launch_frames_parse(q.parse->stream, q.parse->stream_bytes, q.parse->frame_off, n, q.parse->flags,
+                                   q.parse->body_off, q.parse->body_len, q.parse->hdr_crc, q.parse->pre, s));
+  // stamp (frames stamp): likewise the stamp's bounds / cap check, and the fold
+  // then writes the headers (stamped set; the caller skips its stamp launch).
+  const bool fuse_stamp = q.stamp && route_all && g_big_aligned;
+  if (q.stamp && !fuse_stamp) RPCCRC_TRY(launch_frames_stamp_prep(*q.stamp, n, s));
+  ItemsArgs a = items_args(c, q.base, q.offsets, q.lengths, n, 0, 0, q.mode, q.out);
+  if (q.err) a.err = q.err;
   if (packed) {
     const uint64_t ms = std::min<uint64_t>(kPackedMaxSlices, std::max<uint64_t>(8192, 4 * n));
-    size_t bytes = 0;
-    RPCCRC_TRY(packed_workspace_bytes(n, ms, &bytes));
-    Lease ws;
-    if (const int rc = ws.get(c.ws, bytes, s)) return rc;
+    size_t scan = 0;
+    RPCCRC_TRY(packed_scan_bytes(n, &scan));
     PackedBatch p;
-    p.base = base;
-    p.offsets = offsets;
-    p.lengths = lengths;
+    Lease ws;
     p.n = n;
-    p.mode = mode;
+    p.max_slices = ms;
+    if (const int rc = ws.get(c.ws, s, [&](WsLayout &w) { packed_layout(w, scan, &p); })) return rc;
+    p.base = q.base;
+    p.offsets = q.offsets;
+    p.lengths = q.lengths;
+    p.mode = q.mode;
     p.lds_image = c.img;
     p.tq = c.tq;
-    p.out = out;
-    p.ws = ws.ptr();
-    p.ws_bytes = bytes;
-    p.max_slices = ms;
+    p.out = q.out;
     p.min_slice = packed_min_slice();
     return map_hip(launch_packed_batch(p, nt, mb, s));
   }
-  size_t split_bytes = 0;
-  if (split) RPCCRC_TRY(split_workspace_bytes(n, &split_bytes));
-  split_bytes = (split_bytes + 255) & ~(size_t)255;
+  size_t split_scan = 0;
+  if (split) RPCCRC_TRY(split_scan_bytes(n, &split_scan));
   // Span mode (route-all over a 4 KiB-aligned stream of >= kSpanMinBytes; the
   // plan still falls back to chunks when the bodies are sparse in it).
-  const uint64_t span_rows = (route_all && g_big_span && g_big_aligned && ((uintptr_t)base & 4095u) == 0 &&
-                              span_bytes >= kSpanMinBytes && (span_bytes >> 12) <= kSpanMaxRows)
-                                 ? span_bytes >> 12
+  const uint64_t span_rows = (route_all && g_big_span && g_big_aligned && ((uintptr_t)q.base & 4095u) == 0 &&
+                              q.span_bytes >= kSpanMinBytes && (q.span_bytes >> 12) <= kSpanMaxRows)
+                                 ? q.span_bytes >> 12
                                  : 0;
-  const size_t route_bytes = route ? big_route_workspace_bytes(n, span_rows) : 0;
-  Lease ws;
-  if (split_bytes + route_bytes > 0)
-    if (const int rc = ws.get(c.ws, split_bytes + route_bytes, s)) return rc;
+  SplitWs sw{};
+  BigRoute r{};
+  Lease ws; // the split lists, then the route's arrays
+  if (split || route)
+    if (const int rc = ws.get(c.ws, s, [&](WsLayout &w) {
+          if (split) split_layout(w, n, split_scan, &sw);
+          if (route) big_route_layout(w, n, span_rows, &r);
+        }))
+      return rc;
   // Dense span mode: a ragged batch of many bodies whose bound
   // (or, unbounded, the mode's own 1 MiB body limit) allows it.  The plan
   // decides on the device whether the bodies lie back to back in order with
@@ -803,31 +817,28 @@ int ragged(const DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, con
   // nb_cap: the blocks the workspace holds (20 B each) -- by the bound, or for an
   // unbounded call by a 64 KiB average body (a longer stream is refused by the
   // plan and takes the rows pass and the route: exact, as without the mode)
-  const uint64_t dense_len = max_len ? max_len : kDenseMaxBody;
-  const uint64_t nb_cap = std::min<uint64_t>(n * (max_len ? max_len : 65536u) / 4096u + 2u, kDenseMaxBlocks);
-  const bool dense = dense_enabled() && !route_all && !split && !small_bodies && mode == kModeFinal &&
+  const uint64_t dense_len = q.max_len ? q.max_len : kDenseMaxBody;
+  const uint64_t nb_cap = std::min<uint64_t>(n * (q.max_len ? q.max_len : 65536u) / 4096u + 2u, kDenseMaxBlocks);
+  const bool dense = dense_enabled() && !route_all && !split && !q.small_bodies && q.mode == kModeFinal &&
                      n >= kDenseMinN && n <= kDenseMaxN && dense_len >= kDenseMinBody && dense_len <= kDenseMaxBody &&
                      nb_cap >= 8ull * dyn_round(1) * (uint64_t)mb;
   Lease dws;
   DenseArgs dn{};
   StealLease dsl; // the span pass's steal counter
   if (dense) {
-    if (const int rc = dws.get(c.ws, dense_workspace_bytes(n, nb_cap), s)) return rc;
-    dn = dense_carve(dws.ptr(), n, nb_cap);
-    dn.base = base;
-    dn.offsets = offsets;
-    dn.lengths = lengths;
-    dn.out = out;
+    if (const int rc = dws.get(c.ws, s, [&](WsLayout &w) { dense_layout(w, n, nb_cap, &dn); })) return rc;
+    dn.base = q.base;
+    dn.offsets = q.offsets;
+    dn.lengths = q.lengths;
+    dn.out = q.out;
     dn.tq = c.tq;
     dn.tab = c.dense_tab;
     RPCCRC_TRY(launch_dense_plan(dn, s));
     a.skip_dev = &dn.ctl->skip;
   }
-  BigRoute r{};
   StealLease sl;  // the route's chunk pass deals its tail from this counter (device-counted)
   StealLease ssl; // ... and its span pass from this one
   if (route) {
-    r = big_route_carve(ws.ptr() + split_bytes, n, span_rows);
     r.min_chunk = g_big_chunk;
     r.aligned = g_big_aligned;
     r.tq = c.tq;
@@ -841,35 +852,32 @@ int ragged(const DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, con
       // (the verdicts come from the aligned route's fold only: the end-aligned
       // fold, big_combine_kernel, writes CRCs -- with RPCCRC_BIG_ALIGNED=0 the
       // caller's compare launch writes them)
-      if (cmp && g_big_aligned) {
-        r.cmp_expected = cmp->expected;
-        r.cmp_pre = cmp->pre;
-        r.cmp_verdict = cmp->verdict;
-        if (compared) *compared = true;
+      if (q.cmp && g_big_aligned) {
+        r.cmp_expected = q.cmp->expected;
+        r.cmp_pre = q.cmp->pre;
+        r.cmp_verdict = q.cmp->verdict;
+        q.compared = true;
       }
-      if (fuse_parse) r.parse = *fparse;
+      if (fuse_parse) r.parse = *q.parse;
       if (fuse_stamp) {
-        r.stamp = *fstamp;
-        if (stamped) *stamped = true;
+        r.stamp = *q.stamp;
+        q.stamped = true;
       }
     } else {
       const uint32_t big_min = big_min_for(n);
       if (dense) r.skip = &dn.ctl->skip;
-      RPCCRC_TRY(launch_big_classify(lengths, n, big_min, r, s));
+      RPCCRC_TRY(launch_big_classify(q.lengths, n, big_min, r, s));
       a.routed = r.routed;
       a.big_min = big_min;
     }
-    if (const int rc = c.steal->acquire(s, &sl.slot)) return rc;
-    sl.p = sl.slot->p;
-    sl.pool = c.steal;
-    sl.s = s;
+    if (const int rc = sl.acquire(c, s)) return rc;
     if (span_rows)
       if (const int rc = ssl.get(c, span_rows, 1, s)) return rc;
     a.test_giveup = take_test_giveup(); // (the route's chunk pass; the plain rows pass takes its own below)
   }
   StealLease rsl; // the plain rows pass deals its tail from a steal counter too (RPCCRC_RAGGED_STEAL=0: not)
   if (split) {
-    RPCCRC_TRY(launch_split_batch(a, ws.ptr(), split_bytes, nt, mb, s));
+    RPCCRC_TRY(launch_split_batch(a, sw, nt, mb, s));
   } else if (!route_all && !test_dense_only()) {
     if (ragged_steal()) {
       if (const int rc = rsl.get(c, n, 1, s)) return rc;
@@ -883,7 +891,7 @@ int ragged(const DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, con
   }
   if (dense) {
     ItemsArgs sp = items_args(c, nullptr, nullptr, nullptr, nb_cap, 4096, 4096, kModeRaw, dn.W);
-    if (err) sp.err = err;
+    if (q.err) sp.err = q.err;
     sp.n_dev = &dn.ctl->nblocks;
     sp.lds_image = c.img_span;
     sp.span_ctl = dn.ctl;
@@ -1173,10 +1181,7 @@ uint32_t scalar_small(const DeviceCtx &c, ScalarCtx &t, const uint8_t *src, uint
 
 // RPCCRC_SERVICE=0 turns the service off (every drop-in call launches a kernel).
 bool service_enabled() {
-  static const bool v = [] {
-    const char *e = getenv("RPCCRC_SERVICE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_switch("RPCCRC_SERVICE", true);
   return v;
 }
 constexpr uint64_t kSvcIdleTicks = 200000;   // 2 ms without a request (s_memrealtime, 100 MHz)
@@ -1197,10 +1202,7 @@ constexpr uint64_t kSvcWaitMutedNs = 20000000; // the test build's muted request
 // (their tag never matches) and their first wait 20 ms, to exercise the fallback.
 bool take_test_svc_mute() {
 #ifdef RPCCRC_TEST_HOOKS
-  static std::atomic<long> left{[] {
-    const char *e = getenv("RPCCRC_TEST_SVC_MUTE");
-    return e ? atol(e) : 0L;
-  }()};
+  static std::atomic<long> left{env_count("RPCCRC_TEST_SVC_MUTE")};
   return left.fetch_sub(1) > 0;
 #else
   return false;
@@ -1414,7 +1416,7 @@ uint32_t scalar_crc(const void *data, uint32_t len) {
     // in a device word at the end of the lease and comes back by a 4-byte D2H
     // copy: the chunk combine XORs its partials in with device atomics, which
     // must not target host memory.
-    const size_t body = (len + 255) & ~(size_t)255;
+    const size_t body = align256(len);
     Lease stage;
     if ((rc = stage.get(c->ws, body + 256, t->stream))) die("device staging", rc);
     uint8_t *dbuf = stage.ptr();
@@ -1514,8 +1516,10 @@ int host_batch_run(const DeviceCtx &c, HostPipeline &p, const uint8_t *base, con
     if (hi > lo) RPCCRC_TRY(hipMemcpyAsync(s.dbuf, base + lo, hi - lo, hipMemcpyHostToDevice, s.stream));
     RPCCRC_TRY(hipMemcpyAsync(s.doff, s.hoff, cnt * 8, hipMemcpyHostToDevice, s.stream));
     RPCCRC_TRY(hipMemcpyAsync(s.dlen, s.hlen, cnt * 4, hipMemcpyHostToDevice, s.stream));
-    rc = ragged(c, s.dbuf, s.doff, s.dlen, cnt, kModeFinal, s.dout, s.stream, false, true, p.perr);
-    if (rc) return rc;
+    RaggedCall q{s.dbuf, s.doff, s.dlen, cnt, s.dout};
+    q.route = true;
+    q.err = p.perr;
+    if ((rc = ragged(c, q, s.stream))) return rc;
     RPCCRC_TRY(hipMemcpyAsync(s.hout, s.dout, cnt * 4, hipMemcpyDeviceToHost, s.stream));
     s.first = i;
     s.count = cnt;
@@ -1542,8 +1546,6 @@ int host_batch(DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, const
   return rc;
 }
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ---- gathered bodies -----------------------------------------
 
 // Bodies given as segment lists: the ragged pass CRCs the nseg segments into a
@@ -1554,18 +1556,20 @@ constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 int device_gather(const DeviceCtx &c, const uint8_t *d_base, const uint64_t *d_seg_offsets,
                   const uint32_t *d_seg_lengths, uint64_t nseg, uint32_t max_seg_len, const uint64_t *d_seg_first,
                   uint64_t n, const uint32_t *d_seed, uint32_t *d_out, hipStream_t s) {
-  const size_t crc_bytes = align256(nseg * 4);
-  Lease ws;
-  if (const int rc = ws.get(c.ws, crc_bytes + gather_workspace_bytes(n, nseg), s)) return rc;
-  uint32_t *seg_crc = reinterpret_cast<uint32_t *>(ws.ptr());
-  if (nseg > 0) {
-    const bool route = max_seg_len == 0 || max_seg_len >= big_min_for(nseg); // as rpc_crc32_device_batch_bounded
-    if (const int rc = ragged(c, d_base, d_seg_offsets, d_seg_lengths, nseg, kModeFinal, seg_crc, s, false, route, nullptr, 0,
-                              nullptr, nullptr, nullptr, nullptr, nullptr, max_seg_len))
-      return rc;
-  }
   GatherArgs g{};
-  gather_carve(ws.ptr() + crc_bytes, n, nseg, &g);
+  uint32_t *seg_crc = nullptr;
+  Lease ws;
+  if (const int rc = ws.get(c.ws, s, [&](WsLayout &w) {
+        seg_crc = w.take<uint32_t>(nseg);
+        gather_layout(w, n, nseg, &g);
+      }))
+    return rc;
+  if (nseg > 0) {
+    RaggedCall q{d_base, d_seg_offsets, d_seg_lengths, nseg, seg_crc};
+    q.route = max_seg_len == 0 || max_seg_len >= big_min_for(nseg); // as rpc_crc32_device_batch_bounded
+    q.max_len = max_seg_len;
+    if (const int rc = ragged(c, q, s)) return rc;
+  }
   g.seg_crc = seg_crc;
   g.seg_len = d_seg_lengths;
   g.seg_first = d_seg_first;
@@ -1589,24 +1593,24 @@ int host_gather(DeviceCtx &c, const uint8_t *base, const uint64_t *seg_offsets, 
   int rc = pipe_init(*p);
   if (rc == RPCCRC_OK) {
     hipStream_t s = p->slot[0].stream;
-    const size_t b_crc = align256(nseg * 4), b_len = align256(nseg * 4), b_first = align256((n + 1) * 8),
-                 b_io = align256(n * 4);
+    GatherArgs g{};
+    uint32_t *d_crc = nullptr, *d_len = nullptr, *d_io = nullptr; // d_io: seeds in, CRCs out
+    uint64_t *d_first = nullptr;
     Lease ws;
-    rc = ws.get(c.ws, b_crc + b_len + b_first + b_io + gather_workspace_bytes(n, nseg), s);
+    rc = ws.get(c.ws, s, [&](WsLayout &w) {
+      d_crc = w.take<uint32_t>(nseg);
+      d_len = w.take<uint32_t>(nseg);
+      d_first = w.take<uint64_t>(n + 1);
+      d_io = w.take<uint32_t>(n);
+      gather_layout(w, n, nseg, &g);
+    });
     auto run = [&]() -> int {
-      uint8_t *d = ws.ptr();
-      uint32_t *d_crc = reinterpret_cast<uint32_t *>(d);
-      uint32_t *d_len = reinterpret_cast<uint32_t *>(d + b_crc);
-      uint64_t *d_first = reinterpret_cast<uint64_t *>(d + b_crc + b_len);
-      uint32_t *d_io = reinterpret_cast<uint32_t *>(d + b_crc + b_len + b_first); // seeds in, CRCs out
       if (nseg > 0) {
         RPCCRC_TRY(hipMemcpyAsync(d_crc, seg_crc.data(), nseg * 4, hipMemcpyHostToDevice, s));
         RPCCRC_TRY(hipMemcpyAsync(d_len, seg_lengths, nseg * 4, hipMemcpyHostToDevice, s));
       }
       RPCCRC_TRY(hipMemcpyAsync(d_first, seg_first, (n + 1) * 8, hipMemcpyHostToDevice, s));
       if (seed) RPCCRC_TRY(hipMemcpyAsync(d_io, seed, n * 4, hipMemcpyHostToDevice, s));
-      GatherArgs g{};
-      gather_carve(d + b_crc + b_len + b_first + b_io, n, nseg, &g);
       g.seg_crc = d_crc;
       g.seg_len = d_len;
       g.seg_first = d_first;
@@ -1688,34 +1692,29 @@ static int frames_scan_common(const uint8_t *d_stream, uint64_t stream_bytes, co
   Lease tiled;
   if (tile_cap) {
     const int L = scan_levels_for(tile_cap);
-    size_t bytes = align256(nconn * 8) + align256((nconn + 1) * 8) + 256 + align256(tile_cap * 4) +
-                   align256(tile_cap * 8) + align256((tile_cap + 1) * 8);
-    for (int l = 0; l < L; ++l) {
-      const uint64_t nl = scan_level_count<kScanGroup>(tile_cap, (uint32_t)l);
-      bytes += align256(nl * kScanMapLen * 2) + align256(nl * 2);
-    }
-    if (tiled.get(c->ws, bytes, s) != RPCCRC_OK) {
+    auto layout = [&](WsLayout &w) {
+      a.conn_tiles = w.take<uint64_t>(nconn);
+      a.tbase = w.take<uint64_t>(nconn + 1);
+      a.nt_live = w.take<uint64_t>(32); // (a 256-byte line of its own)
+      a.tconn = w.take<uint32_t>(tile_cap);
+      a.tile_cnt = w.take<uint64_t>(tile_cap);
+      a.tpre = w.take<uint64_t>(tile_cap + 1);
+      for (int l = 0; l < L; ++l) {
+        const uint64_t nl = scan_level_count<kScanGroup>(tile_cap, (uint32_t)l);
+        a.maps[l] = w.take<uint16_t>(nl * kScanMapLen);
+        a.entry[l] = w.take<uint16_t>(nl);
+      }
+    };
+    WsLayout size;
+    layout(size);
+    if (!size.ok() || tiled.get(c->ws, size.used(), s) != RPCCRC_OK) {
       tile_cap = 0; // no workspace: every connection walks serially (results identical)
       (void)hipGetLastError(); // (the failed allocation's error is not the next launch's)
     } else {
-      uint8_t *w = tiled.ptr();
-      auto take = [&w](size_t n) {
-        uint8_t *p = w;
-        w += align256(n);
-        return p;
-      };
+      WsLayout w(tiled.ptr(), size.used());
+      layout(w);
+      if (!w.ok()) return RPCCRC_EINVAL;
       a.levels = L;
-      a.conn_tiles = reinterpret_cast<uint64_t *>(take(nconn * 8));
-      a.tbase = reinterpret_cast<uint64_t *>(take((nconn + 1) * 8));
-      a.nt_live = reinterpret_cast<uint64_t *>(take(256));
-      a.tconn = reinterpret_cast<uint32_t *>(take(tile_cap * 4));
-      a.tile_cnt = reinterpret_cast<uint64_t *>(take(tile_cap * 8));
-      a.tpre = reinterpret_cast<uint64_t *>(take((tile_cap + 1) * 8));
-      for (int l = 0; l < L; ++l) {
-        const uint64_t nl = scan_level_count<kScanGroup>(tile_cap, (uint32_t)l);
-        a.maps[l] = reinterpret_cast<uint16_t *>(take(nl * kScanMapLen * 2));
-        a.entry[l] = reinterpret_cast<uint16_t *>(take(nl * 2));
-      }
     }
   }
   a.tile_cap = tile_cap;
@@ -1723,25 +1722,17 @@ static int frames_scan_common(const uint8_t *d_stream, uint64_t stream_bytes, co
   Lease base;
   const size_t tmp_words = scan_tmp_words(std::max(nconn, tile_cap));
   const bool own_conn = reach && !d_frame_conn;
-  const size_t base_bytes = align256(nconn * 8) + align256(tmp_words * 8) + (reach ? align256(nconn * 8) : 0) +
-                            (own_conn ? align256(frame_cap * 4) : 0);
   uint64_t *first_close = nullptr;
-  {
-    // (nconn == 0 runs the same launches: no unit finds work, *d_nframes = 0,
-    // every entry of d_frame_offsets is padding)
-    if ((rc = base.get(c->ws, base_bytes + 256, s))) return rc;
-    uint8_t *w = base.ptr();
-    a.conn_cnt = reinterpret_cast<uint64_t *>(w);
-    w += align256(nconn * 8);
-    a.scan_tmp = reinterpret_cast<uint64_t *>(w);
-    w += align256(tmp_words * 8);
-    if (reach) {
-      first_close = reinterpret_cast<uint64_t *>(w);
-      w += align256(nconn * 8);
-    }
-    if (own_conn) a.frame_conn = reinterpret_cast<uint32_t *>(w);
-    if ((rc = map_hip(launch_frames_scan(a, s)))) return rc;
-  }
+  // (nconn == 0 runs the same launches: no unit finds work, *d_nframes = 0,
+  // every entry of d_frame_offsets is padding)
+  auto base_layout = [&](WsLayout &w) {
+    a.conn_cnt = w.take<uint64_t>(nconn);
+    a.scan_tmp = w.take<uint64_t>(tmp_words);
+    if (reach) first_close = w.take<uint64_t>(nconn);
+    if (own_conn) a.frame_conn = w.take<uint32_t>(frame_cap);
+  };
+  if ((rc = base.get(c->ws, s, base_layout, 256))) return rc;
+  if ((rc = map_hip(launch_frames_scan(a, s)))) return rc;
   if (!fused || frame_cap == 0) return RPCCRC_OK;
   if ((rc = rpc_frames_verify_device(d_stream, stream_bytes, d_frame_offsets, frame_cap, flags, d_verdict, d_crc,
                                      stream)))
@@ -1810,9 +1801,10 @@ int rpc_crc32_device_batch_bounded(const uint8_t *d_base, const uint64_t *d_offs
   // fold after it: ~30 us of launches, profiles/r02final4/c2_kernel_stats.csv)
   // are not launched.  A body over a wrong bound is still CRC'd correctly by
   // the rows pass (one wave for the whole body): the hint is about speed only.
-  const bool route = max_len == 0 || max_len >= big_min_for(n);
-  return ragged(*c, d_base, d_offsets, d_lengths, n, kModeFinal, d_out, static_cast<hipStream_t>(stream), false, route,
-                nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, max_len);
+  RaggedCall q{d_base, d_offsets, d_lengths, n, d_out};
+  q.route = max_len == 0 || max_len >= big_min_for(n);
+  q.max_len = max_len;
+  return ragged(*c, q, static_cast<hipStream_t>(stream));
 }
 
 int rpc_crc32_device_uniform(const uint8_t *d_base, uint64_t n, uint32_t body_len, uint64_t stride, uint32_t *d_out,
@@ -1881,32 +1873,32 @@ int rpc_frames_verify_device(const uint8_t *d_stream, uint64_t stream_bytes, con
   int rc = get_async_ctx(&c);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  Lease wsl;
-  const size_t ws_bytes = align256(n * 8) + 3 * align256(n * 4) + align256(n);
-  if ((rc = wsl.get(c->ws, ws_bytes, s))) return rc;
-  uint8_t *ws = wsl.ptr();
-  uint64_t *boff = reinterpret_cast<uint64_t *>(ws);
-  uint32_t *blen = reinterpret_cast<uint32_t *>(ws + align256(n * 8));
-  uint32_t *bexp = reinterpret_cast<uint32_t *>(ws + align256(n * 8) + align256(n * 4));
-  uint32_t *bcrc = d_crc ? d_crc : reinterpret_cast<uint32_t *>(ws + align256(n * 8) + 2 * align256(n * 4));
-  uint8_t *pre = ws + align256(n * 8) + 3 * align256(n * 4);
   FramesParse fp; // (launched by ragged(), or fused into the route's plan)
+  uint32_t *bcrc = nullptr;
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    fp.body_off = w.take<uint64_t>(n);
+    fp.body_len = w.take<uint32_t>(n);
+    fp.hdr_crc = w.take<uint32_t>(n);
+    bcrc = w.take<uint32_t>(n); // (reserved also when the caller's d_crc takes its place)
+    fp.pre = w.take<uint8_t>(n);
+  });
+  if (rc) return rc;
+  if (d_crc) bcrc = d_crc;
   fp.stream = d_stream;
   fp.stream_bytes = stream_bytes;
   fp.frame_off = d_frame_offsets;
   fp.flags = flags;
-  fp.body_off = boff;
-  fp.body_len = blen;
-  fp.hdr_crc = bexp;
-  fp.pre = pre;
-  const bool lift = (flags & RPC_FRAMES_LIFT_CAP) != 0;
-  const FramesCmp cmp{bexp, pre, d_verdict};
-  bool compared = false;
-  if ((rc = ragged(*c, d_stream, boff, blen, n, kModeFinal, bcrc, s, true, lift, nullptr, stream_bytes, &cmp, &compared,
-                   &fp)))
-    return rc;
-  if (compared) return RPCCRC_OK; // (route-all: the fold wrote the verdicts)
-  return map_hip(launch_frames_compare(bcrc, bexp, pre, n, d_verdict, s));
+  const FramesCmp cmp{fp.hdr_crc, fp.pre, d_verdict};
+  RaggedCall q{d_stream, fp.body_off, fp.body_len, n, bcrc};
+  q.small_bodies = true;
+  q.route = (flags & RPC_FRAMES_LIFT_CAP) != 0;
+  q.span_bytes = stream_bytes;
+  q.cmp = &cmp;
+  q.parse = &fp;
+  if ((rc = ragged(*c, q, s))) return rc;
+  if (q.compared) return RPCCRC_OK; // (route-all: the fold wrote the verdicts)
+  return map_hip(launch_frames_compare(bcrc, fp.hdr_crc, fp.pre, n, d_verdict, s));
 }
 
 int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_frame_offsets,
@@ -1919,15 +1911,17 @@ int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes, const uint
   int rc = get_async_ctx(&c);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  Lease wsl;
-  const size_t ws_bytes = align256(n * 8) + 2 * align256(n * 4) + align256(n);
-  if ((rc = wsl.get(c->ws, ws_bytes, s))) return rc;
-  uint8_t *ws = wsl.ptr();
-  uint64_t *boff = reinterpret_cast<uint64_t *>(ws);
-  uint32_t *blen = reinterpret_cast<uint32_t *>(ws + align256(n * 8));
-  uint32_t *bcrc = reinterpret_cast<uint32_t *>(ws + align256(n * 8) + align256(n * 4));
-  uint8_t *pre = d_verdict ? d_verdict : ws + align256(n * 8) + 2 * align256(n * 4);
   FramesStamp st; // (the check launched by ragged(), or fused into the route's plan; the headers likewise)
+  uint32_t *bcrc = nullptr;
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    st.body_off = w.take<uint64_t>(n);
+    st.len_eff = w.take<uint32_t>(n);
+    bcrc = w.take<uint32_t>(n);
+    st.pre = w.take<uint8_t>(n); // (reserved also when the caller's d_verdict takes its place)
+  });
+  if (rc) return rc;
+  if (d_verdict) st.pre = d_verdict;
   st.stream = d_stream;
   st.stream_bytes = stream_bytes;
   st.frame_off = d_frame_offsets;
@@ -1935,15 +1929,13 @@ int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes, const uint
   st.flags = flags;
   st.version = version;
   st.type = type;
-  st.body_off = boff;
-  st.len_eff = blen;
-  st.pre = pre;
-  const bool lift = (flags & RPC_FRAMES_LIFT_CAP) != 0;
-  bool stamped = false;
-  if ((rc = ragged(*c, d_stream, boff, blen, n, kModeFinal, bcrc, s, true, lift, nullptr, stream_bytes, nullptr,
-                   nullptr, nullptr, &st, &stamped)))
-    return rc;
-  if (stamped) return RPCCRC_OK; // (route-all: the fold wrote the headers)
+  RaggedCall q{d_stream, st.body_off, st.len_eff, n, bcrc};
+  q.small_bodies = true;
+  q.route = (flags & RPC_FRAMES_LIFT_CAP) != 0;
+  q.span_bytes = stream_bytes;
+  q.stamp = &st;
+  if ((rc = ragged(*c, q, s))) return rc;
+  if (q.stamped) return RPCCRC_OK; // (route-all: the fold wrote the headers)
   return map_hip(launch_frames_stamp(st, bcrc, n, s));
 }
 
@@ -1971,17 +1963,19 @@ int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const
     return RPCCRC_OK;
   }
   const size_t tmp_words = scan_tmp_words(n);
-  Lease wsl;
-  const size_t ws_bytes = 2 * align256(n * 8) + align256((n + 1) * 8) + align256(tmp_words * 8) +
-                          2 * align256(n * 4) + align256(n);
-  if ((rc = wsl.get(c->ws, ws_bytes, s))) return rc;
-  uint8_t *w = wsl.ptr();
-  auto take = [&w](size_t bytes) {
-    uint8_t *p = w;
-    w += align256(bytes);
-    return p;
-  };
   PackArgs a;
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    a.sizes = w.take<uint64_t>(n);
+    a.src_off = w.take<uint64_t>(n);
+    a.offs = w.take<uint64_t>(n + 1);
+    a.scan_tmp = w.take<uint64_t>(tmp_words);
+    a.src_len = w.take<uint32_t>(n);
+    a.crc = w.take<uint32_t>(n); // (reserved also when the caller's d_crc takes its place)
+    a.pre = w.take<uint8_t>(n);
+  });
+  if (rc) return rc;
+  if (d_crc) a.crc = d_crc;
   a.bodies = d_bodies;
   a.bodies_bytes = bodies_bytes;
   a.body_off = d_body_offsets;
@@ -2000,14 +1994,6 @@ int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const
   a.verdict = d_verdict;
   a.conn_bytes_first = d_conn_bytes_first;
   a.total = d_total;
-  a.sizes = reinterpret_cast<uint64_t *>(take(n * 8));
-  a.src_off = reinterpret_cast<uint64_t *>(take(n * 8));
-  a.offs = reinterpret_cast<uint64_t *>(take((n + 1) * 8));
-  a.scan_tmp = reinterpret_cast<uint64_t *>(take(tmp_words * 8));
-  a.src_len = reinterpret_cast<uint32_t *>(take(n * 4));
-  uint32_t *own_crc = reinterpret_cast<uint32_t *>(take(n * 4));
-  a.crc = d_crc ? d_crc : own_crc;
-  a.pre = take(n);
   if ((rc = map_hip(launch_frames_pack_layout(a, s)))) return rc;
   // The CRCs, over the source bodies: the ragged call stamp makes (the length
   // bound, the lifted-cap route), without its hooks.  A layout-only call that
@@ -2016,9 +2002,11 @@ int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const
   if (no_data || !d_bodies) { // (no source buffer: every body the CRC pass would read is empty)
     RPCCRC_TRY(hipMemsetAsync(a.crc, 0, n * 4, s));
   } else if (d_out || d_crc) {
-    const bool lift = (flags & RPC_FRAMES_LIFT_CAP) != 0;
-    if ((rc = ragged(*c, d_bodies, a.src_off, a.src_len, n, kModeFinal, a.crc, s, true, lift, nullptr, bodies_bytes)))
-      return rc;
+    RaggedCall q{d_bodies, a.src_off, a.src_len, n, a.crc};
+    q.small_bodies = true;
+    q.route = (flags & RPC_FRAMES_LIFT_CAP) != 0;
+    q.span_bytes = bodies_bytes;
+    if ((rc = ragged(*c, q, s))) return rc;
   }
   return map_hip(launch_frames_pack_write(a, s));
 }

@@ -1128,6 +1128,87 @@ def test_workspace_pool_stream_switches():
         assert rpc_amd.rpc_crc32(host[:100]) == oracle.crc32(host[:100])
 
 
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 129])
+def test_workspace_layout_edges(n):
+    """Every call that carves several arrays out of one leased block (rpc_amd/csrc/workspace.h),
+    at the counts where n, 2n, 4n or 8n bytes sit just under, on and just over a 256-byte
+    step: the smallest shapes at which two mis-carved neighbours overlap.  Bodies of 1-300 B,
+    one process, one stream; every CRC against the oracle, every verdict OK.  (At these sizes
+    the scan's "tiled" setting still walks serially: the stream is shorter than one tile.)"""
+    rng = np.random.default_rng(n)
+    lens = rng.integers(1, 301, n).astype(np.uint32)
+    offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64)
+    total = int(lens.sum())
+    host = np.concatenate([oracle.splitmix_bytes((total + 7) // 8 * 8, 0xED6E + n),
+                           oracle.splitmix_bytes(BIG + 8, 0xB16 + n)])
+    want = oracle.crc32_batch(host, offs, lens)
+    base, d_o, d_l = to_dev(host), to_dev(offs.view(np.int64)), to_dev(lens.view(np.int32))
+    ok = [rpc_amd.FRAME_OK] * n
+    try:
+        # 1. the packed, split and rows workspaces
+        for path in ("packed", "split", "rows"):
+            rpc_amd.set_ragged_path(path)
+            assert np.array_equal(u32(rpc_amd.device_batch(base, d_o, d_l)), want), path
+        rpc_amd.set_ragged_path("auto")
+        # 2. the route's workspace: one more body, over the threshold, unbounded
+        offs_b = np.append(offs, np.uint64((total + 7) // 8 * 8))
+        lens_b = np.append(lens, np.uint32(BIG + 1))
+        got = u32(rpc_amd.device_batch(base, to_dev(offs_b.view(np.int64)), to_dev(lens_b.view(np.int32)), max_len=0))
+        assert np.array_equal(got, oracle.crc32_batch(host, offs_b, lens_b))
+        # 3. the gather fold's: every body cut into three segments (some empty), seeded
+        cut1, cut2 = lens // 3, lens // 3 + lens // 2
+        seg_off = np.stack([offs, offs + cut1, offs + cut2], axis=1).reshape(-1).astype(np.uint64)
+        seg_len = np.stack([cut1, cut2 - cut1, lens - cut2], axis=1).reshape(-1).astype(np.uint32)
+        seeds = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+        seg_crc = oracle.crc32_batch(host, seg_off, seg_len)
+        want_g = []
+        for i in range(n):
+            c = int(seeds[i])
+            for s in range(3 * i, 3 * i + 3):
+                c = oracle.combine(c, int(seg_crc[s]), int(seg_len[s]))
+            want_g.append(c)
+        got = u32(rpc_amd.device_gather(base, to_dev(seg_off.view(np.int64)), to_dev(seg_len.view(np.int32)),
+                                        to_dev((3 * np.arange(n + 1)).astype(np.int64)),
+                                        seed=to_dev(seeds.view(np.int32))))
+        assert got.tolist() == want_g
+        # 4. stamp, then verify, cap lifted: with the library's own verdict / CRC array and with the caller's
+        f_off = (offs + np.uint64(12) * np.arange(n, dtype=np.uint64)).astype(np.uint64)
+        blob = np.zeros(total + 12 * n, dtype=np.uint8)
+        for o, b, ln in zip(f_off, offs, lens):
+            blob[int(o) + 12:int(o) + 12 + int(ln)] = host[int(b):int(b) + int(ln)]
+        d_f, sh = to_dev(f_off.view(np.int64)), rpc_amd._stream_handle(None)
+        lift = rpc_amd.FRAMES_LIFT_CAP
+        own = to_dev(blob)
+        assert rpc_amd._lib.rpc_frames_stamp_device(own.data_ptr(), own.numel(), d_f.data_ptr(), d_l.data_ptr(), n, 1,
+                                                    rpc_amd.RPC_TYPE_DATA, lift, None, sh) == 0
+        v = torch.full((n,), 0xEE, dtype=torch.uint8, device=DEV)
+        assert rpc_amd._lib.rpc_frames_verify_device(own.data_ptr(), own.numel(), d_f.data_ptr(), n,
+                                                     rpc_amd.FRAMES_SERVER | lift, v.data_ptr(), None, sh) == 0
+        assert v.cpu().tolist() == ok
+        mine = to_dev(blob)
+        assert rpc_amd.frames_stamp(mine, d_f, d_l, lift_cap=True).cpu().tolist() == ok
+        assert torch.equal(mine, own)
+        v, c = rpc_amd.frames_verify(mine, d_f, role="client", lift_cap=True)
+        assert v.cpu().tolist() == ok and np.array_equal(u32(c), want)
+        # 5. pack, then the fused scan of what it wrote, as the other side reads it
+        nc = min(n, 7)
+        conn = to_dev((np.arange(nc + 1) * n // nc).astype(np.int64))
+        p = rpc_amd.frames_pack(base, d_o, d_l, conn_first=conn)
+        assert p.total == total + 12 * n and p.verdict.cpu().tolist() == ok and np.array_equal(u32(p.crc), want)
+        assert p.offsets.cpu().numpy().view(np.uint64).tolist() == f_off.tolist()
+        cbf = p.conn_bytes_first
+        for path in ("serial", "tiled"):
+            rpc_amd.set_scan_path(path)
+            r = rpc_amd.frames_scan(p.stream, cbf[:-1].contiguous(), (cbf[1:] - cbf[:-1]).contiguous(), role="client",
+                                    verify=True, max_frames=n)
+            assert r.nframes == n and torch.equal(r.frame_offsets, p.offsets), path
+            assert torch.equal(r.conn_first, conn), path
+            assert r.verdict.cpu().tolist() == ok and np.array_equal(u32(r.crc), want), path
+    finally:
+        rpc_amd.set_ragged_path("auto")
+        rpc_amd.set_scan_path("auto")
+
+
 def test_c3_per_rank_shard_full_coverage():
     """Config C3's per-GPU shard at full size: 8M x 4 KiB = 32 GiB on one GPU (rank 0's
     seed), EVERY CRC against the oracle (threaded, 4 GiB at a time)."""
