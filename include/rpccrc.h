@@ -325,6 +325,73 @@ RPCCRC_API int rpc_frames_scan_verify_device(const uint8_t *d_stream, uint64_t s
 #define RPCCRC_SCAN_TILED 2
 RPCCRC_API int rpc_frames_set_scan_path(int path);
 
+/* ---- frame unpack: verified bodies as C strings, and the reply plan -------
+ * What sits between the fused scan + verify and the dispatcher.  Inputs are
+ * what rpc_frames_scan_verify_device (or scan, then verify) left: the raw
+ * stream, d_frame_offsets and d_verdict over n entries (n may be the padded
+ * frame_cap), the CSR d_conn_first.  The bodies the reference would dispatch
+ * are copied out back to back, each followed by one 0 byte when nul is 1 -- the
+ * reference copies a body into its own buffer, sets body[body_len] = '\0' and
+ * hands the char * to its dispatcher (rpc_server_main.c:198-238,
+ * rpc_async.c:357,454-457) -- and the per-entry arrays are the frame pack's
+ * inputs for the replies.  For entry i with v = d_verdict[i], in this order:
+ *   1. v is neither RPC_FRAME_OK nor RPC_FRAME_CONTROL: nothing is delivered:
+ *      size 0, reply type RPC_FRAME_TYPE_NONE, version 0, length 0, verdict out
+ *      v.  The offset is not looked at (padding entries, NOT_REACHED, BAD_CRC
+ *      and the rest end here).
+ *   2. The 12-byte header does not lie inside [0, stream_bytes): the verdict is
+ *      contradicted: size 0, NONE, version 0, length 0, verdict out
+ *      RPC_FRAME_MALFORMED.
+ *   3. version, type and body_len are read big-endian (rpc_server_main.c:
+ *      165-169).  ctl is PING with RPC_FRAMES_SERVER, PONG with _CLIENT.  Every
+ *      contradiction below gives the result of rule 2.
+ *   4. v == CONTROL: type != ctl is a contradiction; otherwise size 0, length
+ *      0, the header's version, verdict out CONTROL, reply type PONG at a server
+ *      (rpc_server_main.c:172-187 answers a PING with a PONG of its version) and
+ *      NONE at a client, which consumes a PONG (rpc_async.c:303-309).
+ *   5. v == OK: type == ctl, body_len over RPC_MAX_BODY_LEN without
+ *      RPC_FRAMES_LIFT_CAP, body_len 0 at a client, or a body not inside the
+ *      stream is a contradiction; otherwise the entry is delivered: size
+ *      body_len + nul, length body_len, the header's version, reply type
+ *      RPC_FRAME_TYPE_DATA, verdict out OK.
+ * No CRC is computed: OK is trusted as far as rules 2-5 allow.
+ * Layout: d_body_offsets[i] is the exclusive 64-bit sum of the sizes of entries
+ * 0 .. i-1, *d_total the sum of all; d_conn_bytes_first[c] is the body offset
+ * of entry d_conn_first[c], d_conn_bytes_first[nconn] is *d_total (a CSR that
+ * runs past n reads as the end).  The layout never depends on out_cap.
+ * Output: a delivered entry's body bytes go to d_out + d_body_offsets[i]; with
+ * nul one 0 byte follows them, and that address is the string the reference's
+ * rpc_server_dispatch takes.
+ * Capacity (the pack's rule): an entry of non-zero size that does not end
+ * inside out_cap is not written, not even in part; its verdict out becomes
+ * RPC_FRAME_MALFORMED and its reply type NONE; its offset, length and version
+ * keep the layout's values.  Nothing at or beyond d_out + out_cap is written,
+ * and no byte of d_out outside a written entry.  d_out == NULL with out_cap ==
+ * 0 is the layout-only call.
+ * Nothing outside [d_stream, d_stream + stream_bytes) is read.  d_out must not
+ * overlap the stream; d_verdict_out may be d_verdict.
+ * The outputs are rpc_frames_pack_device's inputs unchanged: bodies d_out,
+ * d_body_offsets, d_body_lens, types d_reply_types, versions d_versions, the
+ * same d_conn_first (the pack never looks at the offset or length of a NONE or
+ * PONG entry).
+ * All pointers are device pointers; every output from d_body_offsets on is
+ * optional; the call is asynchronous on `stream`.  flags: exactly one role bit,
+ * optionally RPC_FRAMES_LIFT_CAP.  nul: 0 or 1.
+ * RPCCRC_EINVAL, before any device is touched: unknown flag bits or not exactly
+ * one role bit; nul not 0 or 1; n >= 0xFFFFFFFF; n > 0 with d_frame_offsets or
+ * d_verdict NULL; stream_bytes > 0 with d_stream NULL; out_cap > 0 with d_out
+ * NULL; d_conn_bytes_first without d_conn_first; nconn > 0 with d_conn_first
+ * NULL.  n == 0 with neither d_total nor d_conn_bytes_first is RPCCRC_OK with
+ * no device; with them, *d_total and the nconn + 1 connection words are written
+ * as 0. */
+RPCCRC_API int rpc_frames_unpack_device(const uint8_t *d_stream, uint64_t stream_bytes,
+                           const uint64_t *d_frame_offsets, const uint8_t *d_verdict, uint64_t n,
+                           const uint64_t *d_conn_first, uint64_t nconn, int flags, int nul,
+                           uint8_t *d_out, uint64_t out_cap,
+                           uint64_t *d_body_offsets, uint32_t *d_body_lens, uint16_t *d_reply_types,
+                           uint16_t *d_versions, uint8_t *d_verdict_out,
+                           uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

@@ -40,6 +40,8 @@ __all__ = [
     "frames_stamp",
     "frames_pack",
     "FramePack",
+    "frames_unpack",
+    "FrameUnpack",
     "frames_scan",
     "FrameScan",
     "set_scan_path",
@@ -409,6 +411,82 @@ def frames_pack(bodies, body_offsets, body_lens, types=None, version: int = 1, t
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FramePack(out, offsets, verdict, crc, cbf, nb)
+
+
+class FrameUnpack(NamedTuple):
+    """What frames_unpack returns (device tensors; ``total`` is the host-side byte count, or with
+    a caller's ``out`` -- nothing is read back then -- a one-element int64 device tensor)."""
+    bodies: object            # uint8: the delivered bodies back to back, each followed by a 0 byte with nul
+    body_offsets: object      # int64 [n]: where each entry's body starts (entries of size 0 share the next one's)
+    body_lens: object         # int32 [n]: body_len of a delivered entry, else 0
+    reply_types: object       # int16 [n]: frames_pack's types: DATA / PONG / TYPE_NONE
+    versions: object          # int16 [n]: the request's version, which the reply echoes
+    verdict: object           # uint8 [n]: FRAME_OK (delivered) / _CONTROL / _MALFORMED / the input verdict
+    conn_bytes_first: object  # int64 [nconn + 1], or None without conn_first
+    total: object             # bytes of all delivered entries, whether they fitted or not
+
+
+def frames_unpack(stream_buf, frame_offsets, verdict, role: str = "server", lift_cap: bool = False, nul: bool = True,
+                  conn_first=None, out=None, stream=None, stream_bytes=None):
+    """Verified bodies as C strings and the reply plan (rpc_frames_unpack_device): what sits
+    between ``frames_scan(verify=True)`` and the dispatcher, and what feeds ``frames_pack``.
+
+    ``frame_offsets`` / ``verdict`` (int64/uint64 and uint8 device tensors, n entries; the padded
+    arrays of a scan as they are) say where the frames lie in ``stream_buf`` and what the verify
+    found.  Every FRAME_OK entry whose header agrees is delivered: its body is copied to
+    ``bodies[body_offsets[i] : + body_lens[i]]`` and, with ``nul``, followed by one 0 byte (the
+    string the reference's dispatcher takes).  A heartbeat (FRAME_CONTROL) delivers nothing
+    and gets reply type PONG at a server, TYPE_NONE at a client; everything else gets TYPE_NONE.
+    ``bodies, body_offsets, body_lens, reply_types, versions`` and the same ``conn_first`` go to
+    ``frames_pack`` unchanged.
+
+    ``out=None`` makes the layout-only call first, reads the total (one synchronisation),
+    allocates exactly and unpacks.  With ``out`` (a contiguous uint8 device tensor that does
+    not overlap ``stream_buf``) nothing is read back: entries that do not end inside it are
+    FRAME_MALFORMED / TYPE_NONE and not written, and ``total`` stays on the device."""
+    t = _torch()
+    n = frame_offsets.numel()
+    for name, x, size in (("frame_offsets", frame_offsets, 8), ("verdict", verdict, 1)):
+        if x.numel() != n or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    if conn_first is not None and (conn_first.numel() < 1 or conn_first.element_size() != 8):
+        raise ValueError("conn_first needs nconn + 1 8-byte entries")
+    if out is not None and (out.element_size() != 1 or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 tensor")
+    dev = stream_buf.device
+    nconn = 0 if conn_first is None else conn_first.numel() - 1
+    nbytes = stream_buf.numel() * stream_buf.element_size() if stream_bytes is None else int(stream_bytes)
+    flags = _frames_flags(role, lift_cap)
+    sh = _stream_handle(stream)
+    body_offsets = t.empty(n, dtype=t.int64, device=dev)
+    body_lens = t.empty(n, dtype=t.int32, device=dev)
+    reply_types = t.empty(n, dtype=t.int16, device=dev)
+    versions = t.empty(n, dtype=t.int16, device=dev)
+    verdict_out = t.empty(n, dtype=t.uint8, device=dev)
+    cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
+    total = t.zeros(1, dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    def run(dst, layout_only):
+        outs = (None,) * 6 if layout_only else (ptr(body_offsets), ptr(body_lens), ptr(reply_types), ptr(versions),
+                                                ptr(verdict_out), ptr(cbf))
+        check(_lib.rpc_frames_unpack_device(ptr(stream_buf), nbytes if ptr(stream_buf) else 0, ptr(frame_offsets),
+                                            ptr(verdict), n, None if conn_first is None else conn_first.data_ptr(),
+                                            nconn, flags, 1 if nul else 0, ptr(dst), 0 if dst is None else dst.numel(),
+                                            *outs, total.data_ptr(), sh), "rpc_frames_unpack_device")
+
+    if out is not None:
+        run(out, False)
+        return FrameUnpack(out, body_offsets, body_lens, reply_types, versions, verdict_out, cbf, total)
+    run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
+    if stream is not None:
+        stream.synchronize()
+    nb = int(total.cpu()[0])
+    out = t.empty(nb, dtype=t.uint8, device=dev)
+    run(out, False)
+    return FrameUnpack(out, body_offsets, body_lens, reply_types, versions, verdict_out, cbf, nb)
 
 
 class FrameScan(NamedTuple):

@@ -70,6 +70,8 @@ rpc_frames_stamp_device = _sig(
 )
 rpc_frames_pack_device = _sig("rpc_frames_pack_device", _i32, _vp, _u64, _vp, _vp, _u64, _vp, ctypes.c_uint16, _vp,
                               ctypes.c_uint16, _vp, _u64, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp)
+rpc_frames_unpack_device = _sig("rpc_frames_unpack_device", _i32, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _i32, _i32, _vp,
+                                _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_scan_device = _sig("rpc_frames_scan_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp, _u64, _vp, _vp, _vp,
                               _vp, _vp)
 rpc_frames_scan_verify_device = _sig("rpc_frames_scan_verify_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp,
@@ -117,6 +119,7 @@ EXPORTS = (
     "rpc_frames_verify_device",
     "rpc_frames_stamp_device",
     "rpc_frames_pack_device",
+    "rpc_frames_unpack_device",
     "rpc_frames_scan_device",
     "rpc_frames_scan_verify_device",
     "rpc_frames_set_scan_path",

@@ -37,6 +37,7 @@
 #include "frames.h"
 #include "frames_pack.h"
 #include "frames_scan.h"
+#include "frames_unpack.h"
 
 namespace rpccrc {
 namespace {
@@ -2009,6 +2010,62 @@ int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const
     if ((rc = ragged(*c, q, s))) return rc;
   }
   return map_hip(launch_frames_pack_write(a, s));
+}
+
+int rpc_frames_unpack_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_frame_offsets,
+                             const uint8_t *d_verdict, uint64_t n, const uint64_t *d_conn_first, uint64_t nconn,
+                             int flags, int nul, uint8_t *d_out, uint64_t out_cap, uint64_t *d_body_offsets,
+                             uint32_t *d_body_lens, uint16_t *d_reply_types, uint16_t *d_versions,
+                             uint8_t *d_verdict_out, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
+  if (!frames_flags_ok(flags)) return RPCCRC_EINVAL;
+  if (nul != 0 && nul != 1) return RPCCRC_EINVAL;
+  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_frame_offsets || !d_verdict)) return RPCCRC_EINVAL;
+  if (stream_bytes > 0 && !d_stream) return RPCCRC_EINVAL;
+  if (out_cap > 0 && !d_out) return RPCCRC_EINVAL;
+  if (d_conn_bytes_first && !d_conn_first) return RPCCRC_EINVAL;
+  if (nconn > 0 && !d_conn_first) return RPCCRC_EINVAL;
+  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) { // no entries: every offset is 0
+    if (d_total) RPCCRC_TRY(hipMemsetAsync(d_total, 0, 8, s));
+    if (d_conn_bytes_first) RPCCRC_TRY(hipMemsetAsync(d_conn_bytes_first, 0, (nconn + 1) * 8, s));
+    return RPCCRC_OK;
+  }
+  const size_t tmp_words = scan_tmp_words(n);
+  UnpackArgs a;
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    a.sizes = w.take<uint64_t>(n);
+    a.src_off = w.take<uint64_t>(n);
+    a.offs = w.take<uint64_t>(n + 1);
+    a.scan_tmp = w.take<uint64_t>(tmp_words);
+    a.ver = w.take<uint16_t>(n);
+    a.pre = w.take<uint8_t>(n);
+  });
+  if (rc) return rc;
+  a.stream = d_stream;
+  a.stream_bytes = stream_bytes;
+  a.frame_off = d_frame_offsets;
+  a.verdict_in = d_verdict;
+  a.n = n;
+  a.conn_first = d_conn_first;
+  a.nconn = nconn;
+  a.flags = flags;
+  a.nul = nul;
+  a.out = d_out;
+  a.out_cap = out_cap;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.reply_types = d_reply_types;
+  a.versions = d_versions;
+  a.verdict_out = d_verdict_out;
+  a.conn_bytes_first = d_conn_bytes_first;
+  a.total = d_total;
+  return map_hip(launch_frames_unpack(a, s));
 }
 
 int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
