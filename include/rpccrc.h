@@ -392,6 +392,67 @@ RPCCRC_API int rpc_frames_unpack_device(const uint8_t *d_stream, uint64_t stream
                            uint16_t *d_versions, uint8_t *d_verdict_out,
                            uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream);
 
+/* ---- frame carry: partial frames join the next read ------------------------
+ * What happens between two rounds of scan -> unpack -> handlers -> pack.  The
+ * scan left d_conn_consumed[c]: the rest of connection c, its *tail*, is the
+ * start of a frame whose other bytes the next recv() brings.  The caller lands
+ * the next round's new bytes in another buffer, d_next, with `room` bytes of
+ * headroom in front of each connection's bytes: d_next_at[c] is the offset in
+ * d_next at which connection c's new bytes begin (d_new_len[c] of them; they are
+ * there already or a copy on another stream is still landing them: the call
+ * never looks at them).  The call copies each open connection's tail so that it
+ * ends exactly where the new bytes begin, and writes the next round's
+ * connections, d_next_off / d_next_len, for the scan over d_next.  Only the
+ * tails move: with the cap in force a tail is at most 12 + RPC_MAX_BODY_LEN - 1
+ * bytes (the scan stops only inside a header or a body), which
+ * RPC_FRAMES_CARRY_ROOM covers.
+ * For connection c, in this order:
+ *   1. d_conn_state is given and d_conn_state[c] != RPC_CONN_OPEN:
+ *      RPC_CARRY_CLOSED, next_off = next_len = 0.  Its offset, length and
+ *      consumed are not looked at, and its new bytes are not attached: the
+ *      reference reads nothing more from a peer it has dropped
+ *      (rpc_server_main.c:189-195, 227-233).  (The scan of the empty connection
+ *      reads OPEN again; from then on the slot is the host's to reuse.)
+ *   2. The connection does not lie inside [0, stream_bytes), or consumed > len
+ *      (computed without 64-bit wrap): RPC_CARRY_INVALID, 0 / 0, nothing read.
+ *   3. With tail = len - consumed, at = d_next_at[c], nl = d_new_len ?
+ *      d_new_len[c] : 0: tail > room, tail > at, at > next_bytes or nl >
+ *      next_bytes - at: RPC_CARRY_NO_ROOM, 0 / 0, nothing written.
+ *   4. Otherwise stream bytes [off + consumed, off + len) are copied to d_next
+ *      [at - tail, at); next_off = at - tail, next_len = tail + nl,
+ *      RPC_CARRY_OK.
+ * *d_carried is the sum of the tails written.
+ * Nothing outside [d_stream, d_stream + stream_bytes) is read, not even by an
+ * aligned load window.  No byte of d_next outside a written tail is written,
+ * and none is read and written back: the byte at `at` may be in flight from a
+ * copy on another stream.  The regions [at - room, at) of different connections
+ * must be disjoint (the caller's contract, not checked), and d_next must not
+ * overlap the stream: the caller double-buffers.  d_next_off may be d_conn_off
+ * and d_next_len may be d_conn_len: a connection's words are read before any of
+ * them is overwritten.
+ * room is also the bound that picks the route: up to 4096 one launch does
+ * everything; above it (RPC_FRAMES_LIFT_CAP servers, whose partial body can be
+ * megabytes) tails are copied in 16 KiB chunks dealt out over the whole device.
+ * All pointers are device pointers; d_conn_state, d_new_len, d_status and
+ * d_carried are optional; the call is asynchronous on `stream`.
+ * RPCCRC_EINVAL, before any device is touched: nconn >= 0xFFFFFFFF; nconn > 0
+ * with d_conn_off, d_conn_len, d_conn_consumed, d_next_at, d_next_off or
+ * d_next_len NULL; stream_bytes > 0 with d_stream NULL; next_bytes > 0 with
+ * d_next NULL.  nconn == 0 without d_carried is RPCCRC_OK with no device; with
+ * it, *d_carried is written as 0. */
+#define RPC_FRAMES_CARRY_ROOM 1040u /* >= 12 + RPC_MAX_BODY_LEN - 1, rounded up to 16: enough for any tail with the cap in force */
+#define RPC_CARRY_OK 0u       /* tail (possibly empty) carried, new bytes attached */
+#define RPC_CARRY_CLOSED 1u   /* the connection was closed: nothing carried, nothing attached */
+#define RPC_CARRY_INVALID 2u  /* connection not inside the stream, or consumed > len: nothing read */
+#define RPC_CARRY_NO_ROOM 3u  /* tail > room, or the next connection would not lie inside d_next: nothing written */
+RPCCRC_API int rpc_frames_carry_device(const uint8_t *d_stream, uint64_t stream_bytes,
+                           const uint64_t *d_conn_off, const uint64_t *d_conn_len, const uint64_t *d_conn_consumed,
+                           const uint8_t *d_conn_state, uint64_t nconn,
+                           uint8_t *d_next, uint64_t next_bytes, const uint64_t *d_next_at, uint64_t room,
+                           const uint64_t *d_new_len,
+                           uint64_t *d_next_off, uint64_t *d_next_len, uint8_t *d_status,
+                           uint64_t *d_carried, void *stream);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

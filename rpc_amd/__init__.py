@@ -42,6 +42,9 @@ __all__ = [
     "FramePack",
     "frames_unpack",
     "FrameUnpack",
+    "frames_carry",
+    "FrameCarry",
+    "carry_slots",
     "frames_scan",
     "FrameScan",
     "set_scan_path",
@@ -69,6 +72,11 @@ __all__ = [
     "TYPE_NONE",
     "CONN_OPEN",
     "CONN_CLOSED",
+    "CARRY_ROOM",
+    "CARRY_OK",
+    "CARRY_CLOSED",
+    "CARRY_INVALID",
+    "CARRY_NO_ROOM",
 ]
 
 # reference rpc.h:11-17
@@ -93,6 +101,12 @@ CONN_CLOSED = 1
 FRAMES_SERVER = 0x1
 FRAMES_CLIENT = 0x2
 FRAMES_LIFT_CAP = 0x4
+# frames_carry (include/rpccrc.h RPC_FRAMES_CARRY_ROOM / RPC_CARRY_*)
+CARRY_ROOM = 1040  # >= 12 + MAX_BODY_LEN - 1, a multiple of 16: any tail with the cap in force
+CARRY_OK = 0
+CARRY_CLOSED = 1
+CARRY_INVALID = 2
+CARRY_NO_ROOM = 3
 
 
 def _as_buffer(data) -> tuple[Optional[int], int, object]:
@@ -487,6 +501,75 @@ def frames_unpack(stream_buf, frame_offsets, verdict, role: str = "server", lift
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FrameUnpack(out, body_offsets, body_lens, reply_types, versions, verdict_out, cbf, nb)
+
+
+class FrameCarry(NamedTuple):
+    """What frames_carry returns (device tensors; nothing is read back)."""
+    next_offsets: object  # int64 [nconn]: the next round's connections in next_buf ...
+    next_lengths: object  # int64 [nconn]: ... tail + new bytes (0 / 0 unless status is CARRY_OK)
+    status: object        # uint8 [nconn]: CARRY_OK / _CLOSED / _INVALID / _NO_ROOM
+    carried: object       # int64 [1]: the sum of the tails written
+
+
+def carry_slots(new_lengths, room: int = CARRY_ROOM, align: int = 16):
+    """Where a round's new bytes go in the next buffer: the connections back to back, ``room``
+    bytes of headroom in front of each connection's new bytes, each start a multiple of
+    ``align``.  Returns ``(next_at, total_bytes)``: an int64 array for ``frames_carry`` and the
+    size of the buffer -- a host fills one pinned staging buffer of that size at these positions
+    and does one H2D per round."""
+    nl = np.asarray(new_lengths, dtype=np.int64)
+    if nl.ndim != 1 or (nl < 0).any() or room < 0 or align < 1:
+        raise ValueError("new_lengths must be a list of non-negative lengths, room >= 0, align >= 1")
+    at = np.empty(nl.size, dtype=np.int64)
+    cur = 0
+    for c, n in enumerate(nl.tolist()):
+        at[c] = -(-(cur + room) // align) * align
+        cur = int(at[c]) + n
+    return at, cur
+
+
+def frames_carry(stream_buf, conn_offsets, conn_lengths, consumed, state, next_buf, next_at, room: int = CARRY_ROOM,
+                 new_lengths=None, stream=None):
+    """Partial frames join the next read (rpc_frames_carry_device): what sits between two rounds.
+
+    ``conn_offsets`` / ``conn_lengths`` are the connections a ``frames_scan`` walked in
+    ``stream_buf``, ``consumed`` and ``state`` what it returned (``state=None``: every connection
+    is open).  ``next_buf`` is the next round's buffer, a contiguous uint8 device tensor that does
+    not overlap ``stream_buf``; connection c's ``new_lengths[c]`` new bytes begin at
+    ``next_at[c]`` with at least ``room`` free bytes in front of them (``carry_slots``).  Each
+    open connection's unconsumed tail is copied so that it ends at ``next_at[c]``;
+    ``next_offsets`` / ``next_lengths`` are the connections to scan in ``next_buf``.  The new
+    bytes are never looked at: their H2D may still be in flight on another stream.  All index
+    tensors are int64/uint64 device tensors of nconn entries, ``state`` uint8."""
+    t = _torch()
+    nconn = conn_offsets.numel()
+    for name, x, size, opt in (("conn_offsets", conn_offsets, 8, False), ("conn_lengths", conn_lengths, 8, False),
+                               ("consumed", consumed, 8, False), ("state", state, 1, True),
+                               ("next_at", next_at, 8, False), ("new_lengths", new_lengths, 8, True)):
+        if x is None and opt:
+            continue
+        if x.numel() != nconn or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with nconn = {nconn} elements")
+    for name, x in (("stream_buf", stream_buf), ("next_buf", next_buf)):
+        if x.element_size() != 1 or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous uint8 tensor")
+    if room < 0:
+        raise ValueError("room must not be negative")
+    dev = next_buf.device
+    next_offsets = t.empty(nconn, dtype=t.int64, device=dev)
+    next_lengths = t.empty(nconn, dtype=t.int64, device=dev)
+    status = t.empty(nconn, dtype=t.uint8, device=dev)
+    carried = t.empty(1, dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    check(_lib.rpc_frames_carry_device(ptr(stream_buf), stream_buf.numel() if ptr(stream_buf) else 0, ptr(conn_offsets),
+                                       ptr(conn_lengths), ptr(consumed), ptr(state), nconn, ptr(next_buf),
+                                       next_buf.numel() if ptr(next_buf) else 0, ptr(next_at), int(room),
+                                       ptr(new_lengths), ptr(next_offsets), ptr(next_lengths), ptr(status),
+                                       carried.data_ptr(), _stream_handle(stream)), "rpc_frames_carry_device")
+    return FrameCarry(next_offsets, next_lengths, status, carried)
 
 
 class FrameScan(NamedTuple):

@@ -72,6 +72,8 @@ rpc_frames_pack_device = _sig("rpc_frames_pack_device", _i32, _vp, _u64, _vp, _v
                               ctypes.c_uint16, _vp, _u64, _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_unpack_device = _sig("rpc_frames_unpack_device", _i32, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _i32, _i32, _vp,
                                 _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+rpc_frames_carry_device = _sig("rpc_frames_carry_device", _i32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64,
+                               _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_scan_device = _sig("rpc_frames_scan_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp, _u64, _vp, _vp, _vp,
                               _vp, _vp)
 rpc_frames_scan_verify_device = _sig("rpc_frames_scan_verify_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp,
@@ -120,6 +122,7 @@ EXPORTS = (
     "rpc_frames_stamp_device",
     "rpc_frames_pack_device",
     "rpc_frames_unpack_device",
+    "rpc_frames_carry_device",
     "rpc_frames_scan_device",
     "rpc_frames_scan_verify_device",
     "rpc_frames_set_scan_path",

@@ -35,6 +35,7 @@
 #include "crc32_layout.h"
 #include "crc32_service_math.h"
 #include "frames.h"
+#include "frames_carry.h"
 #include "frames_pack.h"
 #include "frames_scan.h"
 #include "frames_unpack.h"
@@ -2066,6 +2067,58 @@ int rpc_frames_unpack_device(const uint8_t *d_stream, uint64_t stream_bytes, con
   a.conn_bytes_first = d_conn_bytes_first;
   a.total = d_total;
   return map_hip(launch_frames_unpack(a, s));
+}
+
+int rpc_frames_carry_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
+                            const uint64_t *d_conn_len, const uint64_t *d_conn_consumed, const uint8_t *d_conn_state,
+                            uint64_t nconn, uint8_t *d_next, uint64_t next_bytes, const uint64_t *d_next_at,
+                            uint64_t room, const uint64_t *d_new_len, uint64_t *d_next_off, uint64_t *d_next_len,
+                            uint8_t *d_status, uint64_t *d_carried, void *stream) {
+  if (nconn >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (nconn > 0 && (!d_conn_off || !d_conn_len || !d_conn_consumed || !d_next_at || !d_next_off || !d_next_len))
+    return RPCCRC_EINVAL;
+  if (stream_bytes > 0 && !d_stream) return RPCCRC_EINVAL;
+  if (next_bytes > 0 && !d_next) return RPCCRC_EINVAL;
+  if (nconn == 0 && !d_carried) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d_carried) RPCCRC_TRY(hipMemsetAsync(d_carried, 0, 8, s)); // (the kernels add to it)
+  if (nconn == 0) return RPCCRC_OK;
+  CarryArgs a;
+  a.stream = d_stream;
+  a.stream_bytes = stream_bytes;
+  a.conn_off = d_conn_off;
+  a.conn_len = d_conn_len;
+  a.conn_consumed = d_conn_consumed;
+  a.conn_state = d_conn_state;
+  a.nconn = nconn;
+  a.next = d_next;
+  a.next_bytes = next_bytes;
+  a.next_at = d_next_at;
+  a.room = room;
+  a.new_len = d_new_len;
+  a.next_off = d_next_off;
+  a.next_len = d_next_len;
+  a.status = d_status;
+  a.carried = d_carried;
+  // No tail can be longer than room: up to the threshold a group of lanes walks
+  // a whole tail in one launch, and the long route's passes (plan, scan, chunks)
+  // are not launched -- the idea of max_len in rpc_crc32_device_batch_bounded.
+  if (room <= kCarryShortRoom) return map_hip(launch_frames_carry_short(a, s));
+  const size_t tmp_words = scan_tmp_words(nconn);
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    a.cnt = w.take<uint64_t>(nconn);
+    a.offs = w.take<uint64_t>(nconn + 1);
+    a.src = w.take<uint64_t>(nconn);
+    a.dst = w.take<uint64_t>(nconn);
+    a.tail = w.take<uint64_t>(nconn);
+    a.scan_tmp = w.take<uint64_t>(tmp_words);
+  });
+  if (rc) return rc;
+  return map_hip(launch_frames_carry_long(a, s));
 }
 
 int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
