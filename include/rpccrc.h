@@ -453,6 +453,106 @@ RPCCRC_API int rpc_frames_carry_device(const uint8_t *d_stream, uint64_t stream_
                            uint64_t *d_next_off, uint64_t *d_next_len, uint8_t *d_status,
                            uint64_t *d_carried, void *stream);
 
+/* ---- frame route: JSON-RPC envelope, method index, groups --------------------
+ * What sits between the unpack and the handlers.  The reference's dispatcher
+ * parses each whole body to learn its `method` and `id` and then runs a strcmp
+ * chain (rpc_server_skeleton.c:118-160).  This call gives, for every delivered
+ * body, the request's id, the index of its method in the server's table and
+ * where `params` lies, and groups the entries by method, so that a handler runs
+ * once over an array of its requests and the host parses only the `params`
+ * span of requests it is going to answer.  It is not a JSON codec: no tree is
+ * built and no value converted but a digits-only id.  It accepts a strict
+ * subset of what the reference's lenient parser accepts; inside the subset its
+ * answer is the reference's, and everything outside it -- every body the
+ * reference calls a parse error among them -- reads RPC_ROUTE_DEFER and goes
+ * through the full parser on the host as before.
+ * d_bodies, d_body_offsets, d_body_lens and d_reply_types are the unpack's
+ * outputs unchanged (nul 0 or 1: the NUL is never looked at); d_reply_types ==
+ * NULL means every entry is DATA.  The method table is the names back to back
+ * in d_method_names; name m is bytes [d_method_off[m], d_method_off[m + 1]).
+ * For entry i, in this order:
+ *   1. d_reply_types is given and d_reply_types[i] != RPC_FRAME_TYPE_DATA:
+ *      RPC_ROUTE_NONE.  The offset and the length are not looked at.
+ *   2. The body does not lie inside [0, bodies_bytes) (computed without 64-bit
+ *      wrap): RPC_ROUTE_RANGE.  Nothing is read.
+ *   3. RPC_ROUTE_DEFER if len == 0 or len > RPC_ROUTE_MAX_BODY, if the body is
+ *      not strict, if it nests deeper than RPC_ROUTE_MAX_DEPTH (the root object
+ *      is depth 1), or if it has more than RPC_ROUTE_MAX_TOKENS tokens (each of
+ *      { } [ ] , : outside strings, each string, each number or literal).
+ *      Strict: the whole body is one JSON object per RFC 8259 with only space,
+ *      \t, \n, \r as whitespace before it, inside it and after it; numbers
+ *      follow the RFC grammar exactly (no leading zero, digits on both sides of
+ *      a point, digits in an exponent); literals are exactly true, false, null;
+ *      string bytes are >= 0x20 and not '"'; a backslash is followed by one of
+ *      " \ / b f n r t -- any \u defers (the reference rejects some surrogates
+ *      and accepts \u0000); bytes >= 0x80 pass unchecked, as the reference
+ *      copies them.  A 0 byte anywhere defers.
+ *   4. RPC_ROUTE_DEFER if a depth-1 key contains a backslash: keys are compared
+ *      as raw bytes.
+ *   5. The value of the FIRST depth-1 key `id`: absent or not a number: id 0.  A
+ *      number written as digits only with value <= 4294967295: that value.
+ *      Digits only and larger: RPC_ROUTE_INVALID with id 0
+ *      (rpc_server_skeleton.c:131-135).  Any other number form (sign, fraction,
+ *      exponent): RPC_ROUTE_DEFER.
+ *   6. The first depth-1 key `method`: absent, or its value is not a string:
+ *      RPC_ROUTE_INVALID with the id of rule 5.  The string contains a
+ *      backslash: RPC_ROUTE_DEFER.
+ *   7. The method's raw bytes are compared with the table in table order: the
+ *      first equal name gives RPC_ROUTE_CALL and its index, none gives
+ *      RPC_ROUTE_NOT_FOUND.  A table word that is not monotone (off[m] >
+ *      off[m + 1]) or that leaves method_bytes makes that name match nothing.
+ *      The empty name is legal and matches "method":"".
+ *   8. For RPC_ROUTE_CALL, d_params_off / d_params_len are the span, relative
+ *      to the body's first byte, of the first depth-1 `params` value, from its
+ *      first byte to one past its last; 0 / 0 when absent (the reference
+ *      substitutes {}).
+ *
+ *   kind                  d_method             d_id                 d_params_off / _len
+ *   NONE, RANGE, DEFER    RPC_ROUTE_NO_METHOD  0                    0 / 0
+ *   INVALID, NOT_FOUND    RPC_ROUTE_NO_METHOD  rule 5 (0 when rule  0 / 0
+ *                                              5 reads INVALID)
+ *   CALL                  table index          rule 5               rule 8
+ *
+ * Every body in the strict subset parses under the reference's parser to the
+ * tree an RFC parser builds (its nesting limit is 1000), so inside the subset
+ * rules 5-8 are rpc_server_skeleton.c:129-160 and 162-260.
+ * Groups: when d_order and d_group_first are given (both or neither),
+ * d_group_first is a CSR of nmethods + 4 words over nmethods + 3 groups: CALL
+ * by method index, then NOT_FOUND, INVALID, DEFER.  d_order lists the entry
+ * indices group by group, ascending inside each group (a stable counting sort);
+ * NONE and RANGE entries are in no group, and only d_order[0 ..
+ * d_group_first[nmethods + 3]) is written (so n words always suffice).
+ * Nothing outside [d_bodies, d_bodies + bodies_bytes) and the two table arrays
+ * is read, not even by an aligned load window.  All pointers are device
+ * pointers; every output is optional; the call is asynchronous on `stream`.
+ * RPCCRC_EINVAL, before any device is touched: n >= 0xFFFFFFFF; nmethods >
+ * RPC_ROUTE_MAX_METHODS; method_bytes > RPC_ROUTE_MAX_METHOD_BYTES; n > 0 with
+ * d_body_offsets or d_body_lens NULL; bodies_bytes > 0 with d_bodies NULL;
+ * nmethods > 0 with d_method_off NULL; method_bytes > 0 with d_method_names
+ * NULL; exactly one of d_order / d_group_first given.  n == 0 writes the
+ * nmethods + 4 words of d_group_first as 0 when it is given and is otherwise
+ * RPCCRC_OK with no device touched. */
+#define RPC_ROUTE_NONE 0u      /* not a DATA entry: nothing to route */
+#define RPC_ROUTE_CALL 1u      /* a request for method d_method[i] */
+#define RPC_ROUTE_NOT_FOUND 2u /* a request for a method the table does not hold (-32601 from d_id[i]) */
+#define RPC_ROUTE_INVALID 3u   /* no string `method`, or an id above 4294967295 (-32600 from d_id[i]) */
+#define RPC_ROUTE_DEFER 4u     /* outside the strict subset: the host's full parser decides */
+#define RPC_ROUTE_RANGE 5u     /* the body does not lie inside d_bodies: nothing read */
+#define RPC_ROUTE_NO_METHOD 0xFFFFu
+#define RPC_ROUTE_MAX_BODY 1024u /* = RPC_MAX_BODY_LEN */
+#define RPC_ROUTE_MAX_DEPTH 32u
+#define RPC_ROUTE_MAX_TOKENS 256u
+#define RPC_ROUTE_MAX_METHODS 256u
+#define RPC_ROUTE_MAX_METHOD_BYTES 4096u
+RPCCRC_API int rpc_frames_route_device(const uint8_t *d_bodies, uint64_t bodies_bytes,
+                           const uint64_t *d_body_offsets, const uint32_t *d_body_lens,
+                           const uint16_t *d_reply_types, uint64_t n,
+                           const uint8_t *d_method_names, uint32_t method_bytes,
+                           const uint32_t *d_method_off, uint32_t nmethods,
+                           uint8_t *d_kind, uint16_t *d_method, uint32_t *d_id,
+                           uint32_t *d_params_off, uint32_t *d_params_len,
+                           uint32_t *d_order, uint32_t *d_group_first, void *stream);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

@@ -77,6 +77,22 @@ __all__ = [
     "CARRY_CLOSED",
     "CARRY_INVALID",
     "CARRY_NO_ROOM",
+    "frames_route",
+    "FrameRoute",
+    "route_table",
+    "RouteTable",
+    "ROUTE_NONE",
+    "ROUTE_CALL",
+    "ROUTE_NOT_FOUND",
+    "ROUTE_INVALID",
+    "ROUTE_DEFER",
+    "ROUTE_RANGE",
+    "ROUTE_NO_METHOD",
+    "ROUTE_MAX_BODY",
+    "ROUTE_MAX_DEPTH",
+    "ROUTE_MAX_TOKENS",
+    "ROUTE_MAX_METHODS",
+    "ROUTE_MAX_METHOD_BYTES",
 ]
 
 # reference rpc.h:11-17
@@ -107,6 +123,19 @@ CARRY_OK = 0
 CARRY_CLOSED = 1
 CARRY_INVALID = 2
 CARRY_NO_ROOM = 3
+# frames_route (include/rpccrc.h RPC_ROUTE_*)
+ROUTE_NONE = 0
+ROUTE_CALL = 1
+ROUTE_NOT_FOUND = 2
+ROUTE_INVALID = 3
+ROUTE_DEFER = 4
+ROUTE_RANGE = 5
+ROUTE_NO_METHOD = 0xFFFF
+ROUTE_MAX_BODY = 1024
+ROUTE_MAX_DEPTH = 32
+ROUTE_MAX_TOKENS = 256
+ROUTE_MAX_METHODS = 256
+ROUTE_MAX_METHOD_BYTES = 4096
 
 
 def _as_buffer(data) -> tuple[Optional[int], int, object]:
@@ -570,6 +599,84 @@ def frames_carry(stream_buf, conn_offsets, conn_lengths, consumed, state, next_b
                                        ptr(new_lengths), ptr(next_offsets), ptr(next_lengths), ptr(status),
                                        carried.data_ptr(), _stream_handle(stream)), "rpc_frames_carry_device")
     return FrameCarry(next_offsets, next_lengths, status, carried)
+
+
+class RouteTable(NamedTuple):
+    """A server's method table on the device (route_table)."""
+    names: object    # uint8: the names back to back
+    offsets: object  # int32 [nmethods + 1]: name m is names[offsets[m] : offsets[m + 1]]
+    nmethods: int
+
+
+def route_table(names, device=None) -> RouteTable:
+    """The two table tensors of frames_route from ``bytes`` / ``str`` method names (at most
+    ROUTE_MAX_METHODS names and ROUTE_MAX_METHOD_BYTES bytes), in the order that gives a
+    CALL's method index."""
+    t = _torch()
+    raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    if len(raw) > ROUTE_MAX_METHODS or sum(map(len, raw)) > ROUTE_MAX_METHOD_BYTES:
+        raise ValueError(f"at most {ROUTE_MAX_METHODS} names and {ROUTE_MAX_METHOD_BYTES} bytes of names")
+    offs = np.zeros(len(raw) + 1, dtype=np.int32)
+    offs[1:] = np.cumsum([len(r) for r in raw], dtype=np.int64)
+    dev = "cuda" if device is None else device
+    return RouteTable(t.from_numpy(np.frombuffer(b"".join(raw), dtype=np.uint8).copy()).to(dev),
+                      t.from_numpy(offs).to(dev), len(raw))
+
+
+class FrameRoute(NamedTuple):
+    """What frames_route returns (device tensors; nothing is read back)."""
+    kind: object         # uint8 [n]: ROUTE_NONE / _CALL / _NOT_FOUND / _INVALID / _DEFER / _RANGE
+    method: object       # int16 [n]: the table index of a CALL, else ROUTE_NO_METHOD (view as uint16)
+    id: object           # int32 [n]: the request's id (view as uint32)
+    params_off: object   # int32 [n]: a CALL's `params` value, relative to the body's first byte ...
+    params_len: object   # int32 [n]: ... 0 / 0 when the request has none
+    order: object        # int32 [n], or None: entry indices group by group; order[:group_first[-1]] is written
+    group_first: object  # int32 [nmethods + 4], or None: CSR over CALL by method, NOT_FOUND, INVALID, DEFER
+
+
+def frames_route(bodies, body_offsets, body_lens, table: RouteTable, reply_types=None, group: bool = True,
+                 stream=None) -> FrameRoute:
+    """The JSON-RPC envelope of every delivered body (rpc_frames_route_device): what sits between
+    ``frames_unpack`` and the handlers.
+
+    ``bodies, body_offsets, body_lens, reply_types`` are ``frames_unpack``'s outputs unchanged
+    (``reply_types=None``: every entry is DATA).  Per entry: the kind, the index of the method
+    in ``table`` (``route_table``), the id, and where the first top-level ``params`` value lies
+    in the body.  Bodies outside the strict subset of include/rpccrc.h read ROUTE_DEFER: parse
+    those on the host as before.  With ``group`` the entries are also listed group by group
+    (CALL by method index, then NOT_FOUND, INVALID, DEFER; a stable sort), so that a handler
+    runs once over ``order[group_first[m] : group_first[m + 1]]``."""
+    t = _torch()
+    n = body_offsets.numel()
+    for name, x, size, opt in (("body_offsets", body_offsets, 8, False), ("body_lens", body_lens, 4, False),
+                               ("reply_types", reply_types, 2, True)):
+        if x is None and opt:
+            continue
+        if x.numel() != n or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    if bodies.element_size() != 1 or not bodies.is_contiguous():
+        raise ValueError("bodies must be a contiguous uint8 tensor")
+    if table.offsets.numel() != table.nmethods + 1 or table.offsets.element_size() != 4:
+        raise ValueError("table.offsets needs nmethods + 1 4-byte entries")
+    dev = bodies.device
+    kind = t.empty(n, dtype=t.uint8, device=dev)
+    method = t.empty(n, dtype=t.int16, device=dev)
+    rid = t.empty(n, dtype=t.int32, device=dev)
+    poff = t.empty(n, dtype=t.int32, device=dev)
+    plen = t.empty(n, dtype=t.int32, device=dev)
+    order = t.empty(max(n, 1), dtype=t.int32, device=dev) if group else None  # (never a null pointer)
+    first = t.empty(table.nmethods + 4, dtype=t.int32, device=dev) if group else None
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    check(_lib.rpc_frames_route_device(ptr(bodies), bodies.numel() if ptr(bodies) else 0, ptr(body_offsets),
+                                       ptr(body_lens), ptr(reply_types), n, ptr(table.names), table.names.numel(),
+                                       ptr(table.offsets), table.nmethods, ptr(kind), ptr(method), ptr(rid), ptr(poff),
+                                       ptr(plen), order.data_ptr() if group else None,
+                                       first.data_ptr() if group else None, _stream_handle(stream)),
+          "rpc_frames_route_device")
+    return FrameRoute(kind, method, rid, poff, plen, order[:n] if group else None, first)
 
 
 class FrameScan(NamedTuple):

@@ -38,6 +38,7 @@
 #include "frames_carry.h"
 #include "frames_pack.h"
 #include "frames_scan.h"
+#include "frames_route.h"
 #include "frames_unpack.h"
 
 namespace rpccrc {
@@ -2119,6 +2120,61 @@ int rpc_frames_carry_device(const uint8_t *d_stream, uint64_t stream_bytes, cons
   });
   if (rc) return rc;
   return map_hip(launch_frames_carry_long(a, s));
+}
+
+int rpc_frames_route_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
+                            const uint32_t *d_body_lens, const uint16_t *d_reply_types, uint64_t n,
+                            const uint8_t *d_method_names, uint32_t method_bytes, const uint32_t *d_method_off,
+                            uint32_t nmethods, uint8_t *d_kind, uint16_t *d_method, uint32_t *d_id,
+                            uint32_t *d_params_off, uint32_t *d_params_len, uint32_t *d_order,
+                            uint32_t *d_group_first, void *stream) {
+  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (nmethods > RPC_ROUTE_MAX_METHODS || method_bytes > RPC_ROUTE_MAX_METHOD_BYTES) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_body_offsets || !d_body_lens)) return RPCCRC_EINVAL;
+  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
+  if (nmethods > 0 && !d_method_off) return RPCCRC_EINVAL;
+  if (method_bytes > 0 && !d_method_names) return RPCCRC_EINVAL;
+  if ((d_order == nullptr) != (d_group_first == nullptr)) return RPCCRC_EINVAL;
+  if (n == 0 && !d_group_first) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) { // no entries: every group is empty
+    RPCCRC_TRY(hipMemsetAsync(d_group_first, 0, ((size_t)nmethods + 4) * 4, s));
+    return RPCCRC_OK;
+  }
+  RouteArgs a;
+  Lease wsl;
+  if (d_order) { // (without the order outputs none of the grouping passes is launched)
+    const uint64_t cells = (uint64_t)route_buckets(nmethods) * route_workgroups(n);
+    const size_t tmp_words = scan_tmp_words(cells);
+    rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+      a.counts = w.take<uint64_t>(cells);
+      a.offs = w.take<uint64_t>(cells + 1);
+      a.scan_tmp = w.take<uint64_t>(tmp_words);
+      a.bucket = w.take<uint16_t>(n);
+    });
+    if (rc) return rc;
+  }
+  a.bodies = d_bodies;
+  a.bodies_bytes = bodies_bytes;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.types = d_reply_types;
+  a.n = n;
+  a.names = d_method_names;
+  a.method_bytes = method_bytes;
+  a.method_off = d_method_off;
+  a.nmethods = nmethods;
+  a.kind = d_kind;
+  a.method = d_method;
+  a.id = d_id;
+  a.params_off = d_params_off;
+  a.params_len = d_params_len;
+  a.order = d_order;
+  a.group_first = d_group_first;
+  return map_hip(launch_frames_route(a, s));
 }
 
 int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
