@@ -1,6 +1,6 @@
 // rpc_amd/csrc/frames_carry.hip -- device-side frame carry
-// (rpc_frames_carry_device; the rule and the piece resolver: frames_carry.h,
-// DESIGN.md 4.14).
+// (rpc_frames_carry_device; the rule and the piece resolver: frames_carry.h; the
+// lane walker, the search and the masked store: frames_tile.h).
 //
 //   short route: one kernel, a group of lanes per connection
 //   long route:  plan pass -> exclusive scan of the chunk counts -> chunk kernel
@@ -9,6 +9,7 @@
 #include "../../include/rpccrc.h"
 #include "excl_scan.h"
 #include "frames_carry.h"
+#include "frames_tile.h"
 
 namespace rpccrc {
 
@@ -29,42 +30,6 @@ constexpr int kCarryGroup = 16;
 constexpr uint32_t kPiecesPerLane = kCarryChunk / kPackPiece / kCarryThreads;
 static_assert(kPiecesPerLane * kPackPiece * kCarryThreads == kCarryChunk, "a chunk is whole rounds of the workgroup");
 constexpr unsigned kCarryMaxGrid = 1u << 18; // workgroups; they stride over the chunks
-static_assert(kPackWide == 64, "wave_find is one wave64");
-
-struct DevSrc {
-  const uint8_t *b;
-  uint64_t n;
-  __device__ __forceinline__ uint64_t addr() const { return (uint64_t)reinterpret_cast<uintptr_t>(b); }
-  __device__ __forceinline__ uint64_t bytes() const { return n; }
-  __device__ __forceinline__ void block16(uint64_t p, uint32_t w[4]) const {
-    const uint4 v = *reinterpret_cast<const uint4 *>(b + p);
-    w[0] = v.x;
-    w[1] = v.y;
-    w[2] = v.z;
-    w[3] = v.w;
-  }
-  __device__ __forceinline__ uint8_t byte(uint64_t p) const { return b[p]; }
-};
-
-// A partial piece: whole words where the mask has them, single bytes otherwise.
-// Plain stores of exactly the masked bytes; nothing is read.
-__device__ __forceinline__ void store_piece(uint8_t *dst, const PackPiece &p) {
-  if (p.mask == 0xFFFFu) {
-    *reinterpret_cast<uint4 *>(dst) = make_uint4(p.w[0], p.w[1], p.w[2], p.w[3]);
-    return;
-  }
-#pragma unroll
-  for (uint32_t j = 0; j < 4; ++j) {
-    const uint32_t m = (p.mask >> (4 * j)) & 15u;
-    if (m == 15u) {
-      *reinterpret_cast<uint32_t *>(dst + 4 * j) = p.w[j];
-    } else {
-#pragma unroll
-      for (uint32_t b = 0; b < 4; ++b)
-        if ((m >> b) & 1u) dst[4 * j + b] = (uint8_t)(p.w[j] >> (8 * b));
-    }
-  }
-}
 
 // The connection's words, then the rule.  Only the state of a closed connection
 // is read.
@@ -144,23 +109,10 @@ __global__ __launch_bounds__(256) void carry_plan_kernel(CarryArgs a) {
   add_carried(a.carried, mine);
 }
 
-// pack_find over all n entries by one whole wave (frames_pack.hip's wave_find).
-// Every lane of the wave calls it with the same x; off[0] = 0 <= x.
-__device__ __forceinline__ uint64_t wave_find(const uint64_t *off, uint64_t n, uint64_t x) {
-  const uint32_t lane = threadIdx.x & 63u;
-  uint64_t lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const uint64_t probe = pack_wide_probe(lo, hi, lane);
-    const bool le = probe <= hi && off[probe] <= x;
-    pack_wide_step(&lo, &hi, (uint32_t)__popcll(__ballot(le)));
-  }
-  return lo;
-}
-
 // One workgroup per chunk (striding when the grid is smaller): wave 0 finds the
-// chunk's connection, then every lane produces its pieces: the whole ones with
-// the block loads of all of them issued before any is used, the tail's first and
-// last piece and those whose window would leave the stream through carry_piece.
+// chunk's connection, then every lane produces its pieces (tile_walk): the whole
+// ones through the window, the tail's first and last piece and those whose
+// window would leave the stream through carry_piece.
 __global__ __launch_bounds__(kCarryThreads) void carry_chunk_kernel(CarryArgs a) {
   __shared__ uint64_t s_conn;
   const uint64_t total = a.offs[a.nconn];
@@ -177,53 +129,22 @@ __global__ __launch_bounds__(kCarryThreads) void carry_chunk_kernel(CarryArgs a)
     const uint32_t mis = carry_mis(d, kCarryChunk);
     const uint64_t start = (ch - a.offs[c]) * kCarryChunk; // of the chunk, from the aligned address d - mis
     uint8_t *const d0 = reinterpret_cast<uint8_t *>(static_cast<uintptr_t>(d - mis + start));
-    const auto piece_at = [&](uint32_t k) { return ((uint64_t)k * kCarryThreads + threadIdx.x) * kPackPiece; };
-    uint64_t blk[kPiecesPerLane];
-    uint32_t shift[kPiecesPerLane];
-    uint32_t fast = 0, slow = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kPiecesPerLane; ++k) {
-      const PackSpan ps = pack_span(start + piece_at(k), kPackPiece, mis, tail);
-      blk[k] = 0;
-      shift[k] = 0;
-      if (ps.x0 < ps.x1) {
-        PackWin w{false, 0, 0};
-        if (carry_piece_is_whole(ps)) w = pack_win_plan(src, s0 + ps.x0, 0);
-        if (w.ok) {
-          fast |= 1u << k;
-          blk[k] = w.blk;
-          shift[k] = w.k;
-        } else {
-          slow |= 1u << k;
-        }
-      }
-    }
-    uint4 l0[kPiecesPerLane], l1[kPiecesPerLane];
-#pragma unroll
-    for (uint32_t k = 0; k < kPiecesPerLane; ++k) {
-      if ((fast >> k) & 1u) {
-        l0[k] = *reinterpret_cast<const uint4 *>(a.stream + blk[k]);
-        l1[k] = *reinterpret_cast<const uint4 *>(a.stream + blk[k] + 16);
-      }
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < kPiecesPerLane; ++k) {
-      if ((fast >> k) & 1u) {
-        uint32_t win[4];
-        pack_win_select8(l0[k].x, l0[k].y, l0[k].z, l0[k].w, l1[k].x, l1[k].y, l1[k].z, l1[k].w, shift[k], win);
-        *reinterpret_cast<uint4 *>(d0 + piece_at(k)) = make_uint4(win[0], win[1], win[2], win[3]);
-      }
-    }
-    for (; slow; slow &= slow - 1) {
-      const uint32_t k = (uint32_t)__ffs((int)slow) - 1u;
-      const PackSpan ps = pack_span(start + piece_at(k), kPackPiece, mis, tail);
-      store_piece(d0 + piece_at(k), carry_piece(src, s0, ps));
-    }
+    const auto piece_at = [&](uint32_t k) { return tile_piece(k, kCarryThreads); };
+    tile_walk<kPiecesPerLane>(
+        a.stream, d0, piece_at,
+        [&](uint32_t k) {
+          const PackSpan ps = pack_span(start + piece_at(k), kPackPiece, mis, tail);
+          TilePlan p{ps.x0 < ps.x1, {false, 0, 0}};
+          if (p.some && carry_piece_is_whole(ps)) p.w = pack_win_plan(src, s0 + ps.x0, 0);
+          return p;
+        },
+        [&](uint32_t k) {
+          const PackSpan ps = pack_span(start + piece_at(k), kPackPiece, mis, tail);
+          store_piece(d0 + piece_at(k), carry_piece(src, s0, ps));
+        });
     __syncthreads(); // s_conn is rewritten for the next chunk
   }
 }
-
-dim3 grid_of(uint64_t n, int threads) { return dim3((unsigned)(n ? (n + threads - 1) / threads : 1)); }
 
 } // namespace
 

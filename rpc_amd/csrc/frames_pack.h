@@ -294,6 +294,14 @@ PACK_HD PackSpan pack_span(uint64_t start, uint64_t nbytes, uint32_t mis, uint64
 PACK_HD uint64_t pack_tiles(uint64_t limit, uint32_t mis, uint32_t tile) {
   return limit ? (limit + mis + tile - 1) / tile : 0;
 }
+// The finish pass's connection rule: the output byte at which connection i
+// begins, i <= nconn (i == nconn: the end).  conn_first is the CSR over the n
+// entries; one that runs past them reads as the end.
+template <class Off>
+PACK_HD uint64_t pack_conn_begin(const Off &off, const uint64_t *conn_first, uint64_t i, uint64_t nconn, uint64_t n) {
+  const uint64_t f = i < nconn ? conn_first[i] : n;
+  return off(f < n ? f : n);
+}
 
 #if defined(__HIPCC__)
 // ---- device side (frames_pack.hip) -----------------------------------------

@@ -1,5 +1,7 @@
 // rpc_amd/csrc/frames_pack.hip -- device-side frame pack (rpc_frames_pack_device;
-// the rules and the piece resolver: frames_pack.h).
+// the rules and the piece resolver: frames_pack.h; the tile range, the lane
+// walker, the search and the store it shares with the unpack and the carry:
+// frames_tile.h).
 //
 //   size pass -> exclusive scan (the layout) -> [CRC pass over the source
 //   bodies, the caller's ragged() call] -> pack kernel -> finish pass
@@ -7,7 +9,7 @@
 
 #include "../../include/rpccrc.h"
 #include "excl_scan.h"
-#include "frames_pack.h"
+#include "frames_tile.h"
 
 namespace rpccrc {
 
@@ -26,8 +28,6 @@ constexpr int kPackThreads = 256;
 constexpr uint32_t kPiecesPerLane = kPackTile / kPackPiece / kPackThreads;
 static_assert(kPiecesPerLane * kPackPiece * kPackThreads == kPackTile, "a tile is whole rounds of the workgroup");
 constexpr unsigned kPackMaxGrid = 1u << 18; // workgroups; they stride over the tiles
-constexpr uint32_t kPackLdsEntries = 1536;  // entries a tile stages in LDS (offsets and source offsets: 24 KiB)
-static_assert(kPackWide == 64, "wave_find is one wave64");
 
 // ---- size pass: one lane per entry -------------------------------------------
 __global__ __launch_bounds__(256) void pack_size_kernel(PackArgs a) {
@@ -48,17 +48,6 @@ __global__ __launch_bounds__(256) void pack_size_kernel(PackArgs a) {
 }
 
 // ---- pack kernel ---------------------------------------------------------------
-// The layout, from global memory or from the tile's own slice staged in LDS
-// (two types, so that each read is a plain global or LDS load, not a flat one).
-struct DevOff {
-  const uint64_t *o;
-  __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return o[i]; }
-};
-struct LdsOff {
-  const uint64_t *lds;
-  uint64_t base;
-  __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return lds[(uint32_t)(i - base)]; }
-};
 struct DevEnt {
   const uint64_t *src_off;
   const uint32_t *src_len, *crc;
@@ -71,45 +60,6 @@ struct DevEnt {
     pack_header_words(v, t, src_len[e], crc[e], h); // (a heartbeat's length and CRC are 0 here)
   }
 };
-struct DevSrc {
-  const uint8_t *b;
-  uint64_t n;
-  __device__ __forceinline__ uint64_t addr() const { return (uint64_t)reinterpret_cast<uintptr_t>(b); }
-  __device__ __forceinline__ uint64_t bytes() const { return n; }
-  __device__ __forceinline__ void block16(uint64_t p, uint32_t w[4]) const {
-    const uint4 v = *reinterpret_cast<const uint4 *>(b + p);
-    w[0] = v.x;
-    w[1] = v.y;
-    w[2] = v.z;
-    w[3] = v.w;
-  }
-  __device__ __forceinline__ uint8_t byte(uint64_t p) const { return b[p]; }
-};
-
-// pack_find over all n entries by one whole wave: the 64 lanes probe 64 evenly
-// spaced entries per round (4 rounds for 16M entries instead of 24 dependent
-// loads).  Every lane of the wave calls it with the same x; off[0] = 0 <= x.
-__device__ __forceinline__ uint64_t wave_find(const uint64_t *off, uint64_t n, uint64_t x) {
-  const uint32_t lane = threadIdx.x & 63u;
-  uint64_t lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const uint64_t probe = pack_wide_probe(lo, hi, lane);
-    const bool le = probe <= hi && off[probe] <= x;
-    pack_wide_step(&lo, &hi, (uint32_t)__popcll(__ballot(le)));
-  }
-  return lo;
-}
-
-__device__ __forceinline__ void store_piece(uint8_t *dst, const PackPiece &p) {
-  if (p.mask == 0xFFFFu) {
-    *reinterpret_cast<uint4 *>(dst) = make_uint4(p.w[0], p.w[1], p.w[2], p.w[3]);
-  } else if (p.mask) { // a stream end, out_cap, or the edge of a frame that is not written: bytewise
-    for (uint32_t b = 0; b < kPackPiece; ++b) {
-      const uint32_t w = b < 4 ? p.w[0] : b < 8 ? p.w[1] : b < 12 ? p.w[2] : p.w[3];
-      if ((p.mask >> b) & 1u) dst[b] = (uint8_t)(w >> (8 * (b & 3)));
-    }
-  }
-}
 
 // One tile's pieces (steps 3 and 4 below), over the readers of the layout and
 // of the entries' source offsets.
@@ -117,77 +67,43 @@ template <class Off>
 __device__ __forceinline__ void pack_tile(const PackArgs &a, const Off off, const Off src_of, const DevEnt &ent, const DevSrc &src,
                                           uint8_t *out0, uint64_t tile, uint32_t mis, uint64_t tile_x1, uint64_t lo0,
                                           uint64_t hi) {
-  const auto piece_at = [&](uint32_t k) {
-    return tile * kPackTile + ((uint64_t)k * kPackThreads + threadIdx.x) * kPackPiece;
-  };
-  uint64_t blk[kPiecesPerLane]; // source offsets of the first blocks
-  uint32_t shift[kPiecesPerLane];
-  uint32_t fast = 0, slow = 0; // bit k: piece k takes the fast path / goes through pack_piece
+  const auto piece_at = [&](uint32_t k) { return tile * kPackTile + tile_piece(k, kPackThreads); };
   uint64_t lo = lo0;
-#pragma unroll
-  for (uint32_t k = 0; k < kPiecesPerLane; ++k) {
-    const PackSpan ps = pack_span(piece_at(k), kPackPiece, mis, tile_x1);
-    blk[k] = 0;
-    shift[k] = 0;
-    if (ps.x0 < ps.x1) {
-      const uint64_t e = pack_find(off, lo, hi, ps.x0);
-      const uint64_t fo = off(e), fe = off(e + 1);
-      lo = e; // (the lane's next piece lies further on)
-      PackWin w{false, 0, 0};
-      if (pack_piece_is_body(fo, fe, ps.x0, ps.x1, ps.b0, a.out_cap))
-        w = pack_win_plan(src, src_of(e) + (ps.x0 - fo - kPackHeaderLen), 0);
-      if (w.ok) {
-        fast |= 1u << k;
-        blk[k] = w.blk;
-        shift[k] = w.k;
-      } else {
-        slow |= 1u << k;
-      }
-    }
-  }
-  uint4 l0[kPiecesPerLane], l1[kPiecesPerLane];
-#pragma unroll
-  for (uint32_t k = 0; k < kPiecesPerLane; ++k) {
-    if ((fast >> k) & 1u) {
-      l0[k] = *reinterpret_cast<const uint4 *>(a.bodies + blk[k]);
-      l1[k] = *reinterpret_cast<const uint4 *>(a.bodies + blk[k] + 16);
-    }
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < kPiecesPerLane; ++k) {
-    if ((fast >> k) & 1u) {
-      uint32_t win[4];
-      pack_win_select8(l0[k].x, l0[k].y, l0[k].z, l0[k].w, l1[k].x, l1[k].y, l1[k].z, l1[k].w, shift[k], win);
-      *reinterpret_cast<uint4 *>(out0 + piece_at(k)) = make_uint4(win[0], win[1], win[2], win[3]);
-    }
-  }
-  // (not unrolled: the resolver is long and few pieces come here.  Each lane
-  // walks its own set bits, so a wave makes as many rounds as its busiest lane
-  // has such pieces -- mostly one -- not one round per k.)
-  for (; slow; slow &= slow - 1) {
-    const uint32_t k = (uint32_t)__ffs((int)slow) - 1u;
-    const PackSpan ps = pack_span(piece_at(k), kPackPiece, mis, tile_x1);
-    uint64_t last;
-    store_piece(out0 + piece_at(k), pack_piece(off, ent, src, lo0, hi, ps.x0, ps.x1, ps.b0, a.out_cap, &last));
-  }
+  tile_walk<kPiecesPerLane>(
+      a.bodies, out0, piece_at,
+      [&](uint32_t k) {
+        const PackSpan ps = pack_span(piece_at(k), kPackPiece, mis, tile_x1);
+        TilePlan p{ps.x0 < ps.x1, {false, 0, 0}};
+        if (p.some) {
+          const uint64_t e = pack_find(off, lo, hi, ps.x0);
+          const uint64_t fo = off(e), fe = off(e + 1);
+          lo = e; // (the lane's next piece lies further on)
+          if (pack_piece_is_body(fo, fe, ps.x0, ps.x1, ps.b0, a.out_cap))
+            p.w = pack_win_plan(src, src_of(e) + (ps.x0 - fo - kPackHeaderLen), 0);
+        }
+        return p;
+      },
+      [&](uint32_t k) {
+        const PackSpan ps = pack_span(piece_at(k), kPackPiece, mis, tile_x1);
+        uint64_t last;
+        store_piece(out0 + piece_at(k), pack_piece(off, ent, src, lo0, hi, ps.x0, ps.x1, ps.b0, a.out_cap, &last));
+      });
 }
 
 // One workgroup per tile of kPackTile output bytes (striding when the grid is
 // smaller); every lane produces kPiecesPerLane aligned 16-byte pieces, a whole
 // wave writing 1 KiB of consecutive bytes per round.  Per tile:
 //  1. waves 0 and 1 find the entries covering its first and last byte;
-//  2. the layout and the source offsets of those entries go to LDS (when they
-//     fit: a tile of heartbeats has 1366 of them, more only with runs of
-//     zero-size entries), so the lanes' own searches cost LDS reads, not
-//     dependent global loads;
+//  2. the layout and the source offsets of those entries go to LDS when they fit
+//     (steps 1 and 2: tile_range);
 //  3. every lane resolves all its pieces; for those that are sixteen body bytes
 //     of one frame (pack_piece_is_body: nearly all) it issues the block loads of
 //     all of them before it uses any, then shifts and stores;
 //  4. the other pieces -- headers, frame edges, stream ends -- go through
-//     pack_piece one by one.
+//     pack_piece one by one (steps 3 and 4: tile_walk).
 __global__ __launch_bounds__(kPackThreads) void pack_kernel(PackArgs a) {
   __shared__ uint64_t s_range[2];
-  __shared__ uint64_t s_off[kPackLdsEntries], s_src[kPackLdsEntries];
+  __shared__ uint64_t s_off[kTileLdsEntries], s_src[kTileLdsEntries];
   const uint64_t total = a.offs[a.n];
   const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(a.out) & 15u);
   uint8_t *const out0 = a.out - mis; // 16-byte aligned; bytes before a.out are never touched
@@ -197,24 +113,11 @@ __global__ __launch_bounds__(kPackThreads) void pack_kernel(PackArgs a) {
   const DevSrc src{a.bodies, a.bodies_bytes};
   for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const PackSpan ts = pack_span(tile * kPackTile, kPackTile, mis, total); // x0 < x1: the tile holds a byte
-    const uint32_t wave = threadIdx.x >> 6;
-    if (wave < 2) { // the entries covering the tile's first and last byte
-      const uint64_t e = wave_find(a.offs, a.n, wave == 0 ? ts.x0 : ts.x1 - 1);
-      if ((threadIdx.x & 63u) == 0) s_range[wave] = e;
-    }
-    __syncthreads();
-    const uint64_t lo0 = s_range[0], hi = s_range[1];
-    const uint64_t want = hi + 2 - lo0; // offsets lo0 .. hi + 1
-    const uint32_t staged = want <= kPackLdsEntries ? (uint32_t)want : 0u;
-    for (uint32_t i = threadIdx.x; i < staged; i += kPackThreads) {
-      s_off[i] = a.offs[lo0 + i];
-      if (i + 1 < staged) s_src[i] = a.src_off[lo0 + i]; // (entries lo0 .. hi: one fewer than the offsets)
-    }
-    __syncthreads();
-    if (staged)
-      pack_tile(a, LdsOff{s_off, lo0}, LdsOff{s_src, lo0}, ent, src, out0, tile, mis, ts.x1, lo0, hi);
+    const TileRange r = tile_range<kPackThreads>(a.offs, a.src_off, a.n, ts.x0, ts.x1 - 1, s_range, s_off, s_src);
+    if (r.staged)
+      pack_tile(a, LdsOff{s_off, r.lo0}, LdsOff{s_src, r.lo0}, ent, src, out0, tile, mis, ts.x1, r.lo0, r.hi);
     else
-      pack_tile(a, DevOff{a.offs}, DevOff{a.src_off}, ent, src, out0, tile, mis, ts.x1, lo0, hi);
+      pack_tile(a, DevOff{a.offs}, DevOff{a.src_off}, ent, src, out0, tile, mis, ts.x1, r.lo0, r.hi);
     __syncthreads(); // s_range, s_off and s_src are rewritten for the next tile
   }
 }
@@ -229,14 +132,9 @@ __global__ __launch_bounds__(256) void pack_finish_kernel(PackArgs a) {
     if (a.frame_off) a.frame_off[i] = at;
     if (a.verdict) a.verdict[i] = pack_final_verdict(a.pre[i], at, a.offs[i + 1] - at, a.out_cap);
   }
-  if (a.conn_bytes_first && i <= a.nconn) {
-    uint64_t f = i < a.nconn ? a.conn_first[i] : a.n;
-    if (f > a.n) f = a.n; // (a CSR that runs past the entries reads as the end)
-    a.conn_bytes_first[i] = a.offs[f];
-  }
+  if (a.conn_bytes_first && i <= a.nconn)
+    a.conn_bytes_first[i] = pack_conn_begin(DevOff{a.offs}, a.conn_first, i, a.nconn, a.n);
 }
-
-dim3 grid_of(uint64_t n, int threads) { return dim3((unsigned)(n ? (n + threads - 1) / threads : 1)); }
 
 } // namespace
 

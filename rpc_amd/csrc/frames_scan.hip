@@ -7,6 +7,7 @@
 // d_conn_first and d_nframes, and the units walk again and write.
 #include "../../include/rpccrc.h"
 #include "frames_scan.h"
+#include "frames_tile.h" // grid_of
 
 namespace rpccrc {
 
@@ -304,8 +305,6 @@ __global__ __launch_bounds__(256) void reach_rewrite_kernel(const uint32_t *fram
     state[c] = RPC_CONN_CLOSED;
   }
 }
-
-dim3 grid_of(uint64_t n, int threads) { return dim3((unsigned)(n ? (n + threads - 1) / threads : 1)); } // (never 0 blocks)
 
 #define SCAN_LAUNCH(kernel, grid, block, ...)                      \
   do {                                                             \

@@ -1641,6 +1641,23 @@ bool frames_flags_ok(int flags) {
          (role == RPC_FRAMES_SERVER || role == RPC_FRAMES_CLIENT);
 }
 
+// What rpc_frames_pack_device and rpc_frames_unpack_device ask of the arguments
+// they have in common.
+bool frames_layout_args_ok(uint64_t n, const uint8_t *d_out, uint64_t out_cap, const uint64_t *d_conn_first,
+                           uint64_t nconn, const uint64_t *d_conn_bytes_first) {
+  if (n >= 0xFFFFFFFFull) return false;
+  if (out_cap > 0 && !d_out) return false;
+  if (d_conn_bytes_first && !d_conn_first) return false;
+  return nconn == 0 || d_conn_first;
+}
+
+// Their empty batch: every offset is 0.
+int frames_layout_empty(uint64_t *d_total, uint64_t *d_conn_bytes_first, uint64_t nconn, hipStream_t s) {
+  if (d_total) RPCCRC_TRY(hipMemsetAsync(d_total, 0, 8, s));
+  if (d_conn_bytes_first) RPCCRC_TRY(hipMemsetAsync(d_conn_bytes_first, 0, (nconn + 1) * 8, s));
+  return RPCCRC_OK;
+}
+
 } // namespace
 } // namespace rpccrc
 
@@ -1948,23 +1965,16 @@ int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const
                            int flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_frame_offsets, uint8_t *d_verdict,
                            uint32_t *d_crc, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
   if ((flags & ~(RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT | RPC_FRAMES_LIFT_CAP)) != 0) return RPCCRC_EINVAL;
-  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
   const bool no_data = !d_types && !pack_is_data(type); // heartbeats or nothing: no body is looked at
   if (n > 0 && !no_data && (!d_body_lens || !d_body_offsets)) return RPCCRC_EINVAL;
   if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
-  if (out_cap > 0 && !d_out) return RPCCRC_EINVAL;
-  if (d_conn_bytes_first && !d_conn_first) return RPCCRC_EINVAL;
-  if (nconn > 0 && !d_conn_first) return RPCCRC_EINVAL;
   if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
   DeviceCtx *c = nullptr;
   int rc = get_async_ctx(&c);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) { // no entries: every offset is 0
-    if (d_total) RPCCRC_TRY(hipMemsetAsync(d_total, 0, 8, s));
-    if (d_conn_bytes_first) RPCCRC_TRY(hipMemsetAsync(d_conn_bytes_first, 0, (nconn + 1) * 8, s));
-    return RPCCRC_OK;
-  }
+  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
   const size_t tmp_words = scan_tmp_words(n);
   PackArgs a;
   Lease wsl;
@@ -2021,22 +2031,15 @@ int rpc_frames_unpack_device(const uint8_t *d_stream, uint64_t stream_bytes, con
                              uint8_t *d_verdict_out, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
   if (!frames_flags_ok(flags)) return RPCCRC_EINVAL;
   if (nul != 0 && nul != 1) return RPCCRC_EINVAL;
-  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
   if (n > 0 && (!d_frame_offsets || !d_verdict)) return RPCCRC_EINVAL;
   if (stream_bytes > 0 && !d_stream) return RPCCRC_EINVAL;
-  if (out_cap > 0 && !d_out) return RPCCRC_EINVAL;
-  if (d_conn_bytes_first && !d_conn_first) return RPCCRC_EINVAL;
-  if (nconn > 0 && !d_conn_first) return RPCCRC_EINVAL;
   if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
   DeviceCtx *c = nullptr;
   int rc = get_async_ctx(&c);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) { // no entries: every offset is 0
-    if (d_total) RPCCRC_TRY(hipMemsetAsync(d_total, 0, 8, s));
-    if (d_conn_bytes_first) RPCCRC_TRY(hipMemsetAsync(d_conn_bytes_first, 0, (nconn + 1) * 8, s));
-    return RPCCRC_OK;
-  }
+  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
   const size_t tmp_words = scan_tmp_words(n);
   UnpackArgs a;
   Lease wsl;

@@ -17,49 +17,20 @@
 // The stream reader aborts on any byte outside [0, stream_bytes); the writer
 // aborts on any byte outside a tail that is to be written, on a byte written
 // twice and, at the end, on a byte of such a tail that was left out.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <fstream>
 #include <iterator>
 #include <string>
-#include <vector>
 
 #include "../../rpc_amd/csrc/frames_carry.h"
+#include "emu_common.h"
 
 using namespace rpccrc;
 
 namespace {
 
-[[noreturn]] void die(const char *what) {
-  fprintf(stderr, "carry_emu: %s\n", what);
-  abort();
-}
+const char kProg[] = "carry_emu";
+[[noreturn]] void die(const char *what) { emu::die(kProg, what); }
 
-struct Off {
-  const std::vector<uint64_t> *o;
-  uint64_t operator()(uint64_t i) const {
-    if (i >= o->size()) die("offset read outside the chunk layout");
-    return (*o)[i];
-  }
-};
-struct Src { // the stream at a pretended address
-  const std::vector<uint8_t> *b;
-  uint64_t base;
-  uint64_t addr() const { return base; }
-  uint64_t bytes() const { return b->size(); }
-  uint8_t byte(uint64_t p) const {
-    if (p >= b->size()) die("stream byte read outside [0, stream_bytes)");
-    return (*b)[p];
-  }
-  void block16(uint64_t p, uint32_t w[4]) const {
-    if ((base + p) & 15u) die("block16 at an unaligned address");
-    if (p > b->size() || b->size() - p < 16) die("stream block read outside [0, stream_bytes)");
-    memcpy(w, b->data() + p, 16); // (little-endian host)
-  }
-};
 struct Conn {
   uint64_t off, len, consumed, state, at, nl;
 };
@@ -88,7 +59,8 @@ int main(int argc, char **argv) {
     while (cf >> c.off >> c.len >> c.consumed >> c.state >> c.at >> c.nl) conns.push_back(c);
   }
   const uint64_t n = conns.size();
-  const Src src{&stream, 4096 + src_mis};
+  const emu::Src src{kProg, &stream, 4096 + src_mis, "stream byte read outside [0, stream_bytes)",
+                     "stream block read outside [0, stream_bytes)"};
 
   // the rule, as plan_of() in the kernels: only the state of a closed connection is looked at
   std::vector<CarryPlan> plan(n);
@@ -154,22 +126,10 @@ int main(int argc, char **argv) {
   } else { // long route: chunk counts, exclusive scan, a workgroup per chunk
     std::vector<uint64_t> offs(n + 1, 0);
     for (uint64_t c = 0; c < n; ++c) offs[c + 1] = offs[c] + carry_chunks(plan[c].tail, next_base + plan[c].next_off, chunk);
-    const Off off{&offs};
+    const emu::Off off{kProg, &offs, "offset read outside the chunk layout"};
     for (uint64_t ch = 0; ch < offs[n]; ++ch) {
-      uint64_t lo = 0, hi = n - 1; // the wave-wide search, and the plain one it must agree with
-      while (lo < hi) {
-        uint32_t cnt = 0;
-        for (uint32_t lane = 0; lane < kPackWide; ++lane) {
-          const uint64_t probe = pack_wide_probe(lo, hi, lane);
-          const bool le = probe <= hi && off(probe) <= ch;
-          if (le && cnt != lane) die("wide search: the lanes that say yes are not a prefix");
-          cnt += le;
-        }
-        pack_wide_step(&lo, &hi, cnt);
-      }
-      if (lo != pack_find(off, 0, n - 1, ch)) die("wide search disagrees with the binary search");
-      if (!(off(lo) <= ch && ch < off(lo + 1))) die("the connection found does not hold the chunk");
-      const uint64_t c = lo;
+      // the wave-wide search, and the plain one it must agree with
+      const uint64_t c = emu::wide_find(off, n, ch, "the connection found does not hold the chunk");
       const uint64_t d = next_base + plan[c].next_off;
       const uint32_t mis = carry_mis(d, chunk);
       const uint64_t start = (ch - off(c)) * chunk;
@@ -188,9 +148,6 @@ int main(int argc, char **argv) {
     printf("%llu %llu %u\n", (unsigned long long)plan[c].next_off, (unsigned long long)plan[c].next_len,
            (unsigned)plan[c].status);
   printf("carried %llu\n", (unsigned long long)carried);
-  FILE *of = fopen(argv[10], "wb");
-  if (!of) die("cannot write the out file");
-  if (next_bytes && fwrite(out.data(), 1, next_bytes, of) != next_bytes) die("short write");
-  fclose(of);
+  emu::write_out(kProg, argv[10], out);
   return 0;
 }

@@ -16,26 +16,18 @@
 // The source reader aborts on any byte outside [0, bodies_bytes); the output
 // writer aborts on any byte outside a frame that is to be written, on a byte
 // written twice and, at the end, on a byte of a written frame that was left out.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <fstream>
 #include <iterator>
 #include <string>
-#include <vector>
 
-#include "../../rpc_amd/csrc/frames_pack.h"
+#include "emu_common.h"
 
 using namespace rpccrc;
 
 namespace {
 
-[[noreturn]] void die(const char *what) {
-  fprintf(stderr, "pack_emu: %s\n", what);
-  abort();
-}
+const char kProg[] = "pack_emu";
+[[noreturn]] void die(const char *what) { emu::die(kProg, what); }
 
 uint32_t crc32_bitwise(const uint8_t *p, uint64_t n) {
   uint32_t c = 0xFFFFFFFFu;
@@ -46,34 +38,12 @@ uint32_t crc32_bitwise(const uint8_t *p, uint64_t n) {
   return ~c;
 }
 
-struct Off {
-  const std::vector<uint64_t> *o;
-  uint64_t operator()(uint64_t i) const {
-    if (i >= o->size()) die("offset read outside the layout");
-    return (*o)[i];
-  }
-};
 struct Ent {
   const std::vector<uint64_t> *src_off;
   const std::vector<uint32_t> *src_len, *crc, *type, *version;
   uint64_t src(uint64_t e) const { return (*src_off)[e]; }
   void header(uint64_t e, uint32_t h[3]) const {
     pack_header_words((*version)[e], (*type)[e], (*src_len)[e], (*crc)[e], h);
-  }
-};
-struct Src { // the source buffer at a pretended address
-  const std::vector<uint8_t> *b;
-  uint64_t base;
-  uint64_t addr() const { return base; }
-  uint64_t bytes() const { return b->size(); }
-  uint8_t byte(uint64_t p) const {
-    if (p >= b->size()) die("source byte read outside [0, bodies_bytes)");
-    return (*b)[p];
-  }
-  void block16(uint64_t p, uint32_t w[4]) const {
-    if ((base + p) & 15u) die("block16 at an unaligned address");
-    if (p > b->size() || b->size() - p < 16) die("source block read outside [0, bodies_bytes)");
-    memcpy(w, b->data() + p, 16); // (little-endian host)
   }
 };
 
@@ -142,31 +112,17 @@ int main(int argc, char **argv) {
   };
 
   // pack kernel: tiles and pieces aligned to the output's address
-  const Off off{&offs};
+  const emu::Off off{kProg, &offs, "offset read outside the layout"};
   const Ent ent{&src_off, &src_len, &crc, &type, &version};
-  const Src src{&bodies, 4096 + src_mis};
+  const emu::Src src{kProg, &bodies, 4096 + src_mis, "source byte read outside [0, bodies_bytes)",
+                     "source block read outside [0, bodies_bytes)"};
   const uint64_t ntiles = n ? pack_tiles(total < out_cap ? total : out_cap, mis, tile) : 0;
   for (uint64_t t = 0; t < ntiles; ++t) {
     const PackSpan ts = pack_span(t * tile, tile, mis, total);
     if (ts.x0 >= ts.x1) die("a tile with no byte");
-    uint64_t range[2];
-    for (int side = 0; side < 2; ++side) { // the wave-wide search, and the plain one it must agree with
-      const uint64_t x = side == 0 ? ts.x0 : ts.x1 - 1;
-      uint64_t lo = 0, hi = n - 1;
-      while (lo < hi) {
-        uint32_t cnt = 0;
-        for (uint32_t lane = 0; lane < kPackWide; ++lane) {
-          const uint64_t probe = pack_wide_probe(lo, hi, lane);
-          const bool le = probe <= hi && off(probe) <= x;
-          if (le && cnt != lane) die("wide search: the lanes that say yes are not a prefix");
-          cnt += le;
-        }
-        pack_wide_step(&lo, &hi, cnt);
-      }
-      if (lo != pack_find(off, 0, n - 1, x)) die("wide search disagrees with the binary search");
-      if (!(off(lo) <= x && x < off(lo + 1))) die("the entry found does not cover the byte");
-      range[side] = lo;
-    }
+    // the wave-wide search, and the plain one it must agree with
+    const uint64_t range[2] = {emu::wide_find(off, n, ts.x0, "the entry found does not cover the byte"),
+                               emu::wide_find(off, n, ts.x1 - 1, "the entry found does not cover the byte")};
     const uint32_t pieces = tile / kPackPiece, lanes = pieces < 256 ? pieces : 256;
     for (uint32_t lane = 0; lane < lanes; ++lane) {
       uint64_t lo = range[0];
@@ -207,11 +163,9 @@ int main(int argc, char **argv) {
     printf("%llu %u %u\n", (unsigned long long)offs[i], (unsigned)pack_final_verdict(pre[i], offs[i], size[i], out_cap),
            (unsigned)crc[i]);
   printf("conn");
-  for (uint64_t f : conn_first) printf(" %llu", (unsigned long long)offs[f > n ? n : f]);
+  for (size_t c = 0; c < conn_first.size(); ++c)
+    printf(" %llu", (unsigned long long)pack_conn_begin(off, conn_first.data(), c, conn_first.size() - 1, n));
   printf("\n");
-  FILE *of = fopen(argv[9], "wb");
-  if (!of) die("cannot write the out file");
-  if (out_cap && fwrite(out.data(), 1, out_cap, of) != out_cap) die("short write");
-  fclose(of);
+  emu::write_out(kProg, argv[9], out);
   return 0;
 }
