@@ -553,6 +553,95 @@ RPCCRC_API int rpc_frames_route_device(const uint8_t *d_bodies, uint64_t bodies_
                            uint32_t *d_params_off, uint32_t *d_params_len,
                            uint32_t *d_order, uint32_t *d_group_first, void *stream);
 
+/* ---- frame reply: JSON-RPC reply bodies built from id + value ----------------
+ * What sits between the handlers and the pack.  Every reply the reference's
+ * dispatcher sends has one of two fixed forms around a variable part
+ * (rpc_server_helpers.c:10-54, printed by cJSON_PrintUnformatted):
+ *   {"jsonrpc":"2.0","id":<id>,"result":<value>}
+ *   {"jsonrpc":"2.0","id":<id>,"error":{"code":<code>,"message":"<message>"}}
+ * with <id> a uint32_t and <code> an int in plain decimal, and it only ever
+ * sends five messages: Parse error (-32700), Invalid Request (-32600), Method
+ * not found (-32601), Invalid params (-32602), Internal error (-32603)
+ * (rpc_server_skeleton.c:118-260).  So a handler hands back only the value
+ * text, and this call wraps it with the id the route left on the device,
+ * answers the NOT_FOUND and INVALID groups without the host seeing them, lays
+ * the bodies out back to back and leaves the pack's inputs ready.
+ * d_kind and d_id are the route's outputs unchanged; d_kind == NULL means every
+ * DATA entry is a CALL.  d_reply_types is the unpack's output unchanged; NULL
+ * means every entry is DATA.  d_status[i] is the handler's verdict for a CALL: 0
+ * a result, anything else the JSON-RPC error code; NULL means all 0.  Entry i's
+ * value is d_values [d_value_offsets[i], + d_value_lens[i]).
+ * For entry i, in this order:
+ *   1. d_reply_types is given and d_reply_types[i] != RPC_FRAME_TYPE_DATA: size
+ *      0, type out d_reply_types[i] (a PONG stays a PONG for the pack, NONE stays
+ *      NONE), RPC_REPLY_NONE.  Nothing else of the entry is looked at.
+ *   2. Kind RPC_ROUTE_NONE, RPC_ROUTE_RANGE or any value above it: size 0, type
+ *      out RPC_FRAME_TYPE_NONE, RPC_REPLY_NONE.
+ *   3. Kind NOT_FOUND: the error form with code -32601 and d_id[i]; kind
+ *      INVALID: with code -32600 (the route has set d_id to 0 where the
+ *      reference answers with id 0).  Neither d_status nor the value is looked
+ *      at.  RPC_REPLY_ERROR.
+ *   4. Kind CALL, with s = d_status ? d_status[i] : 0:
+ *      s == 0: the result form around the value bytes, copied verbatim -- they
+ *        are the caller's JSON text; nothing is validated or escaped -- and an
+ *        empty value is written as null (this call's choice: the reference
+ *        never has an empty result).  RPC_REPLY_RESULT.
+ *      s one of the five codes above: the error form with that code and its
+ *        fixed message; the value is not looked at.  RPC_REPLY_ERROR.
+ *      any other s: the error form with code s printed as %d and the value
+ *        bytes verbatim as the message (the caller has escaped them); an empty
+ *        value gives the message `error`, the reference's default for a NULL
+ *        message (rpc_server_helpers.c:29).  RPC_REPLY_ERROR.
+ *   5. Kind DEFER: the host ran the full parser and built the whole reply: the
+ *      body is the value bytes verbatim, RPC_REPLY_RAW.  An empty value means
+ *      the host sends nothing: size 0, type NONE, RPC_REPLY_NONE.  d_status is
+ *      not looked at.
+ *   6. A value that rules 4-5 look at and that does not lie inside [0,
+ *      values_bytes) (offset <= values_bytes and length <= values_bytes -
+ *      offset, computed without 64-bit wrap; an empty value is held to it too),
+ *      or a body whose length would not fit 32 bits: size 0, type NONE,
+ *      RPC_REPLY_RANGE.  Nothing is read.
+ * Layout: d_body_offsets[i] is the exclusive 64-bit sum of the sizes of entries
+ * 0 .. i-1, d_body_lens[i] the size, *d_total the sum of all;
+ * d_conn_bytes_first[c] is the body offset of entry d_conn_first[c],
+ * d_conn_bytes_first[nconn] is *d_total (a CSR that runs past n reads as the
+ * end).  The layout never depends on out_cap.
+ * Capacity (the pack's rule): an entry of non-zero size that does not end
+ * inside out_cap is not written, not even in part; it reads RPC_REPLY_NO_ROOM
+ * with type NONE; its offset and length keep the layout's values.  No byte of
+ * d_out outside a written entry is written.  d_out == NULL with out_cap == 0 is
+ * the layout-only call.
+ * Nothing outside [d_values, d_values + values_bytes) is read, not even by an
+ * aligned load window.  d_out must not overlap d_values; d_types_out may be
+ * d_reply_types.
+ * The outputs are rpc_frames_pack_device's inputs unchanged: bodies d_out,
+ * d_body_offsets, d_body_lens, types d_types_out (with the unpack's versions and
+ * the same d_conn_first).  The length cap stays the pack's business (TOO_LARGE
+ * there).
+ * All pointers are device pointers; every output from d_body_offsets on is
+ * optional; the call is asynchronous on `stream`.
+ * RPCCRC_EINVAL, before any device is touched: n >= 0xFFFFFFFF; n > 0 with
+ * d_id, d_value_offsets or d_value_lens NULL; values_bytes > 0 with d_values
+ * NULL; out_cap > 0 with d_out NULL; d_conn_bytes_first without d_conn_first;
+ * nconn > 0 with d_conn_first NULL.  n == 0 with neither d_total nor
+ * d_conn_bytes_first is RPCCRC_OK with no device; with them, *d_total and the
+ * nconn + 1 connection words are written as 0. */
+#define RPC_REPLY_NONE 0u    /* nothing to send for this entry */
+#define RPC_REPLY_RESULT 1u  /* the result form */
+#define RPC_REPLY_ERROR 2u   /* the error form */
+#define RPC_REPLY_RAW 3u     /* a deferred entry: the host's whole reply, verbatim */
+#define RPC_REPLY_RANGE 4u   /* the value does not lie inside d_values, or the body is over 32 bits: nothing read */
+#define RPC_REPLY_NO_ROOM 5u /* the entry does not end inside out_cap: nothing written */
+RPCCRC_API int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const int32_t *d_status,
+                           const uint16_t *d_reply_types, uint64_t n,
+                           const uint8_t *d_values, uint64_t values_bytes,
+                           const uint64_t *d_value_offsets, const uint32_t *d_value_lens,
+                           const uint64_t *d_conn_first, uint64_t nconn,
+                           uint8_t *d_out, uint64_t out_cap,
+                           uint64_t *d_body_offsets, uint32_t *d_body_lens, uint16_t *d_types_out,
+                           uint8_t *d_reply_status, uint64_t *d_conn_bytes_first, uint64_t *d_total,
+                           void *stream);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

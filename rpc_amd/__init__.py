@@ -93,6 +93,14 @@ __all__ = [
     "ROUTE_MAX_TOKENS",
     "ROUTE_MAX_METHODS",
     "ROUTE_MAX_METHOD_BYTES",
+    "frames_reply",
+    "FrameReply",
+    "REPLY_NONE",
+    "REPLY_RESULT",
+    "REPLY_ERROR",
+    "REPLY_RAW",
+    "REPLY_RANGE",
+    "REPLY_NO_ROOM",
 ]
 
 # reference rpc.h:11-17
@@ -136,6 +144,13 @@ ROUTE_MAX_DEPTH = 32
 ROUTE_MAX_TOKENS = 256
 ROUTE_MAX_METHODS = 256
 ROUTE_MAX_METHOD_BYTES = 4096
+# frames_reply (include/rpccrc.h RPC_REPLY_*)
+REPLY_NONE = 0
+REPLY_RESULT = 1
+REPLY_ERROR = 2
+REPLY_RAW = 3
+REPLY_RANGE = 4
+REPLY_NO_ROOM = 5
 
 
 def _as_buffer(data) -> tuple[Optional[int], int, object]:
@@ -677,6 +692,85 @@ def frames_route(bodies, body_offsets, body_lens, table: RouteTable, reply_types
                                        first.data_ptr() if group else None, _stream_handle(stream)),
           "rpc_frames_route_device")
     return FrameRoute(kind, method, rid, poff, plen, order[:n] if group else None, first)
+
+
+class FrameReply(NamedTuple):
+    """What frames_reply returns (device tensors; ``total`` is the host-side byte count, or with
+    a caller's ``out`` -- nothing is read back then -- a one-element int64 device tensor)."""
+    bodies: object            # uint8: the reply bodies back to back
+    body_offsets: object      # int64 [n]: where each entry's body starts (entries of size 0 share the next one's)
+    body_lens: object         # int32 [n]: its length (view as uint32)
+    types: object             # int16 [n]: frames_pack's types: DATA / what reply_types held / TYPE_NONE
+    status: object            # uint8 [n]: REPLY_NONE / _RESULT / _ERROR / _RAW / _RANGE / _NO_ROOM
+    conn_bytes_first: object  # int64 [nconn + 1], or None without conn_first
+    total: object             # bytes of all entries, whether they fitted or not
+
+
+def frames_reply(kind, rid, values, value_offsets, value_lens, status=None, reply_types=None, conn_first=None,
+                 out=None, stream=None) -> FrameReply:
+    """JSON-RPC reply bodies from id + value (rpc_frames_reply_device): what sits between the
+    handlers and ``frames_pack``.
+
+    ``kind`` and ``rid`` are ``frames_route``'s ``kind`` and ``id`` unchanged (``kind=None``: every
+    DATA entry is a CALL), ``reply_types`` is ``frames_unpack``'s (``None``: every entry is DATA).
+    Entry i's value is ``values[value_offsets[i] : + value_lens[i]]``: the JSON text of a CALL's
+    result, wrapped as ``{"jsonrpc":"2.0","id":<id>,"result":<value>}`` (``null`` when empty);
+    with ``status[i] != 0`` the error form with that code -- one of the reference's five codes
+    brings its own message, any other takes the value as the (escaped) message; for a
+    ROUTE_DEFER entry the whole reply the host built, copied verbatim.  NOT_FOUND and INVALID
+    entries are answered from ``rid`` alone.  ``bodies, body_offsets, body_lens, types`` go to
+    ``frames_pack`` unchanged, with the unpack's versions and the same ``conn_first``.
+
+    ``out=None`` makes the layout-only call first, reads the total (one synchronisation),
+    allocates exactly and builds.  With ``out`` (a contiguous uint8 device tensor that does not
+    overlap ``values``) nothing is read back: entries that do not end inside it are
+    REPLY_NO_ROOM / TYPE_NONE and not written, and ``total`` stays on the device."""
+    t = _torch()
+    n = rid.numel()
+    for name, x, size, opt in (("kind", kind, 1, True), ("rid", rid, 4, False), ("status", status, 4, True),
+                               ("reply_types", reply_types, 2, True), ("value_offsets", value_offsets, 8, False),
+                               ("value_lens", value_lens, 4, False)):
+        if x is None and opt:
+            continue
+        if x.numel() != n or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    if values.element_size() != 1 or not values.is_contiguous():
+        raise ValueError("values must be a contiguous uint8 tensor")
+    if conn_first is not None and (conn_first.numel() < 1 or conn_first.element_size() != 8):
+        raise ValueError("conn_first needs nconn + 1 8-byte entries")
+    if out is not None and (out.element_size() != 1 or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 tensor")
+    dev = rid.device
+    nconn = 0 if conn_first is None else conn_first.numel() - 1
+    sh = _stream_handle(stream)
+    body_offsets = t.empty(n, dtype=t.int64, device=dev)
+    body_lens = t.empty(n, dtype=t.int32, device=dev)
+    types = t.empty(n, dtype=t.int16, device=dev)
+    state = t.empty(n, dtype=t.uint8, device=dev)
+    cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
+    total = t.zeros(1, dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    def run(dst, layout_only):
+        outs = (None,) * 5 if layout_only else (ptr(body_offsets), ptr(body_lens), ptr(types), ptr(state), ptr(cbf))
+        check(_lib.rpc_frames_reply_device(ptr(kind), ptr(rid), ptr(status), ptr(reply_types), n, ptr(values),
+                                           values.numel() if ptr(values) else 0, ptr(value_offsets), ptr(value_lens),
+                                           None if conn_first is None else conn_first.data_ptr(), nconn, ptr(dst),
+                                           0 if dst is None else dst.numel(), *outs, total.data_ptr(), sh),
+              "rpc_frames_reply_device")
+
+    if out is not None:
+        run(out, False)
+        return FrameReply(out, body_offsets, body_lens, types, state, cbf, total)
+    run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
+    if stream is not None:
+        stream.synchronize()
+    nb = int(total.cpu()[0])
+    out = t.empty(nb, dtype=t.uint8, device=dev)
+    run(out, False)
+    return FrameReply(out, body_offsets, body_lens, types, state, cbf, nb)
 
 
 class FrameScan(NamedTuple):

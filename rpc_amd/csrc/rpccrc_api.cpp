@@ -38,6 +38,7 @@
 #include "frames_carry.h"
 #include "frames_pack.h"
 #include "frames_scan.h"
+#include "frames_reply.h"
 #include "frames_route.h"
 #include "frames_unpack.h"
 
@@ -2178,6 +2179,55 @@ int rpc_frames_route_device(const uint8_t *d_bodies, uint64_t bodies_bytes, cons
   a.order = d_order;
   a.group_first = d_group_first;
   return map_hip(launch_frames_route(a, s));
+}
+
+int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const int32_t *d_status,
+                            const uint16_t *d_reply_types, uint64_t n, const uint8_t *d_values, uint64_t values_bytes,
+                            const uint64_t *d_value_offsets, const uint32_t *d_value_lens, const uint64_t *d_conn_first,
+                            uint64_t nconn, uint8_t *d_out, uint64_t out_cap, uint64_t *d_body_offsets,
+                            uint32_t *d_body_lens, uint16_t *d_types_out, uint8_t *d_reply_status,
+                            uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
+  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_id || !d_value_offsets || !d_value_lens)) return RPCCRC_EINVAL;
+  if (values_bytes > 0 && !d_values) return RPCCRC_EINVAL;
+  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
+  const size_t tmp_words = scan_tmp_words(n);
+  ReplyArgs a;
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    a.sizes = w.take<uint64_t>(n);
+    a.src_off = w.take<uint64_t>(n);
+    a.offs = w.take<uint64_t>(n + 1);
+    a.scan_tmp = w.take<uint64_t>(tmp_words);
+    a.code = w.take<int32_t>(n);
+    a.meta = w.take<uint16_t>(n);
+  });
+  if (rc) return rc;
+  a.kind = d_kind;
+  a.id = d_id;
+  a.status = d_status;
+  a.reply_types = d_reply_types;
+  a.n = n;
+  a.values = d_values;
+  a.values_bytes = values_bytes;
+  a.value_off = d_value_offsets;
+  a.value_len = d_value_lens;
+  a.conn_first = d_conn_first;
+  a.nconn = nconn;
+  a.out = d_out;
+  a.out_cap = out_cap;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.types_out = d_types_out;
+  a.reply_status = d_reply_status;
+  a.conn_bytes_first = d_conn_bytes_first;
+  a.total = d_total;
+  return map_hip(launch_frames_reply(a, s));
 }
 
 int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
