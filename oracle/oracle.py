@@ -8,6 +8,8 @@ measured or shipped.  The product package ``rpc_amd`` never imports it.
                      (crc32_oracle.c; reference crc.c:4-14 semantics).
 * ``_ref/libref_crc.so`` (optional) the reference's own crc.c compiled in this
                      container + system libz, with a threaded timing harness.
+* ``_ref/ref_dispatch`` (optional) the reference's own rpc_server_dispatch behind our
+                     stdin/stdout driver (ref_dispatch.c): ``ref_dispatch(bodies)``.
 
 Also holds the deterministic synthetic-input generators shared by tests and
 bench (splitmix64 counter stream; JSON-RPC-shaped bodies; log-uniform lengths).
@@ -16,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 import subprocess
 
 import numpy as np
@@ -23,6 +26,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "liboracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libref_crc.so")
+REF_DISPATCH = os.path.join(HERE, "_ref", "ref_dispatch")
 
 
 def _build():
@@ -280,3 +284,29 @@ def ref_available() -> bool:
 
 def load_ref() -> Ref | None:
     return Ref() if ref_available() else None
+
+
+# ---- the reference's dispatcher (optional) ----------------------------------
+
+def ref_dispatch(bodies) -> list | None:
+    """What the reference's own rpc_server_dispatch answers to each body (bytes), each handed
+    over NUL-terminated as its server does: a list of reply bytes, ``None`` in it where the
+    dispatcher returned NULL.  One subprocess per call (oracle/_ref/ref_dispatch, built by
+    oracle/Makefile from ref_dispatch.c and the reference's sources); ``None`` when that binary
+    is missing."""
+    if not os.path.exists(REF_DISPATCH):
+        return None
+    blob = b"".join(struct.pack("<I", len(b)) + bytes(b) for b in bodies)
+    out = subprocess.run([REF_DISPATCH], input=blob, stdout=subprocess.PIPE, check=True).stdout
+    replies, at = [], 0
+    for _ in bodies:
+        (n,) = struct.unpack_from("<I", out, at)
+        at += 4
+        if n == 0xFFFFFFFF:
+            replies.append(None)
+            continue
+        replies.append(out[at:at + n])
+        at += n
+    if at != len(out):  # (a cut last reply leaves `at` behind the end)
+        raise RuntimeError("ref_dispatch: output does not match the framing")
+    return replies

@@ -3,9 +3,14 @@ bodies and the replies rpc_server_dispatch gave for them (its "how" field says h
 recorded).  Wherever the route does not defer, its kind must be the one the recorded reply
 implies and its id the reply's; a body the reference called a parse error must defer.  Two
 conditions keep the comparison from being empty: no canonical body defers, and at least half
-of the hostile class is routed.  Run on the CPU emulator, and on the GPU."""
+of the hostile class is routed.  Run on the CPU emulator, and on the GPU.  The recording can be
+made again: tests/golden/make_route_golden.py writes the fixture from its own bodies with the
+kept driver (oracle/ref_dispatch.c), and a test here asks today's reference for every recorded
+reply."""
 import json
 import os
+import subprocess
+import sys
 
 import pytest
 
@@ -65,6 +70,19 @@ def test_fixture_classes(replies):
     assert any(b'"method":5' in b for b, _ in canon) and any(b'"method"' not in b for b, _ in canon)
     codes = {r["error"]["code"] for _, _, r in replies if "error" in r}
     assert codes >= {-32700, -32600, -32601, -32602}
+
+
+def test_todays_reference_gives_every_recorded_reply():
+    """The fixture is what oracle/_ref/ref_dispatch answers today, reply for reply and byte for
+    byte, and the generator beside it would write the file as it stands."""
+    from route_fuzz import reference
+    doc = json.load(open(os.path.join(HERE, "golden", "route_golden.json")))
+    assert len(doc["entries"]) == 153 and "oracle/ref_dispatch.c" in doc["how"]
+    today = reference([body.encode("latin-1") for _, body, _ in doc["entries"]])
+    for (_, body, reply), now in zip(doc["entries"], today):
+        assert now == reply.encode("latin-1"), (body, reply, now)
+    made = subprocess.run([sys.executable, os.path.join(HERE, "golden", "make_route_golden.py"), "--check"])
+    assert made.returncode == 0
 
 
 def test_rules_agree_with_the_reference(replies):
