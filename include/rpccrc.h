@@ -642,6 +642,88 @@ RPCCRC_API int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_
                            uint8_t *d_reply_status, uint64_t *d_conn_bytes_first, uint64_t *d_total,
                            void *stream);
 
+/* ---- frame resolve: reply envelopes matched to pending ids -------------------
+ * What sits between a client's unpack and its completions.  The reference
+ * client parses each whole reply to learn its `id` and whether `result` or
+ * `error` is there (client/rpc_codec.c:22-52) and completes the one call in
+ * flight on the connection; a client that keeps many calls in flight has to
+ * find the call by id.  This call gives, for every delivered body, the reply's
+ * id, where its `result` and `error` values lie, and which of the caller's
+ * pending slots it answers -- so that the host parses only the spans of calls
+ * it completes.  Like the route it is not a JSON codec and accepts the same
+ * strict subset; everything outside reads RPC_RESOLVE_DEFER and goes through
+ * the full parser on the host as before.
+ * d_bodies, d_body_offsets, d_body_lens and d_reply_types are the unpack's
+ * outputs unchanged (nul 0 or 1: the NUL is never looked at); d_reply_types ==
+ * NULL means every entry is DATA.  d_pending_ids[s] is the id of the call in
+ * the caller's slot s.  For entry i, in this order:
+ *   1. d_reply_types is given and d_reply_types[i] != RPC_FRAME_TYPE_DATA:
+ *      RPC_RESOLVE_NONE.  The offset and the length are not looked at.
+ *   2. The body does not lie inside [0, bodies_bytes) (computed without 64-bit
+ *      wrap): RPC_RESOLVE_RANGE.  Nothing is read.
+ *   3. RPC_RESOLVE_DEFER if the body is outside the route's strict subset: rule
+ *      3 of rpc_frames_route_device word for word, with its three limits
+ *      (RPC_ROUTE_MAX_BODY, RPC_ROUTE_MAX_DEPTH, RPC_ROUTE_MAX_TOKENS).
+ *   4. RPC_RESOLVE_DEFER if a depth-1 key contains a backslash.
+ *   5. Depth-1 keys are compared with `id`, `result` and `error` ignoring ASCII
+ *      letter case, and the FIRST key that matches a name is that name's member
+ *      (cJSON_GetObjectItem; the server's lookup is case-sensitive, so this
+ *      differs from the route).  "ID":"x","id":5 has a string id.
+ *   6. `id` is absent or not a number: RPC_RESOLVE_INVALID (the reference
+ *      returns -1).  A number written as digits only with value <= 4294967295:
+ *      that value.  Any other number form (sign, fraction, exponent), or digits
+ *      only and larger: RPC_RESOLVE_DEFER (the reference casts a double).
+ *   7. d_result_off / d_result_len and d_error_off / d_error_len are the spans
+ *      of the two members' values, relative to the body's first byte, from the
+ *      value's first byte to one past its last; 0 / 0 when absent.  A null
+ *      value is present.  Both, one or neither may be there (the reference
+ *      returns 0 in all four cases).
+ *   8. A decoded entry whose id no slot holds: RPC_RESOLVE_UNKNOWN with
+ *      d_slot[i] = RPC_RESOLVE_NO_SLOT.  Otherwise d_slot[i] is the LOWEST slot
+ *      index holding that id (a table that holds an id twice never matches the
+ *      later slots), and among the entries that name one slot the lowest entry
+ *      index reads RPC_RESOLVE_MATCHED and every other RPC_RESOLVE_DUPLICATE:
+ *      pending_take() called in arrival order, whose second take finds nothing.
+ *   9. d_slot_entry[s] is the matched entry's index, or 0xFFFFFFFF while slot s
+ *      stays open.  d_open lists the open slots in ascending order and *d_nopen
+ *      is their count (both or neither; npending words always suffice).
+ *
+ *   kind                        d_id    spans     d_slot
+ *   NONE, RANGE, DEFER, INVALID 0       0 / 0     RPC_RESOLVE_NO_SLOT
+ *   UNKNOWN                     rule 6  rule 7    RPC_RESOLVE_NO_SLOT
+ *   MATCHED, DUPLICATE          rule 6  rule 7    rule 8
+ *
+ * The result does not depend on the order in which lanes or workgroups run.
+ * npending == 0 is the decode-only call: every decoded entry reads UNKNOWN.
+ * Nothing outside [d_bodies, d_bodies + bodies_bytes) and d_pending_ids[0 ..
+ * npending) is read, not even by an aligned load window.  All pointers are
+ * device pointers; every output is optional; the call is asynchronous on
+ * `stream`.
+ * RPCCRC_EINVAL, before any device is touched: n >= 0xFFFFFFFF; npending >
+ * RPC_RESOLVE_MAX_PENDING; n > 0 with d_body_offsets or d_body_lens NULL;
+ * bodies_bytes > 0 with d_bodies NULL; npending > 0 with d_pending_ids NULL;
+ * exactly one of d_open / d_nopen given.  n == 0 still writes d_slot_entry,
+ * d_open and *d_nopen (every slot open) when they are given and is otherwise
+ * RPCCRC_OK with no device touched. */
+#define RPC_RESOLVE_NONE 0u      /* not a DATA entry: nothing to resolve */
+#define RPC_RESOLVE_MATCHED 1u   /* the reply that completes slot d_slot[i] */
+#define RPC_RESOLVE_UNKNOWN 2u   /* a reply whose id no slot holds */
+#define RPC_RESOLVE_DUPLICATE 3u /* a reply to slot d_slot[i] behind the one that took it */
+#define RPC_RESOLVE_INVALID 4u   /* no numeric `id` (the reference's -1) */
+#define RPC_RESOLVE_DEFER 5u     /* outside the strict subset: the host's full parser decides */
+#define RPC_RESOLVE_RANGE 6u     /* the body does not lie inside d_bodies: nothing read */
+#define RPC_RESOLVE_NO_SLOT 0xFFFFFFFFu
+#define RPC_RESOLVE_MAX_PENDING (1u << 24)
+RPCCRC_API int rpc_frames_resolve_device(const uint8_t *d_bodies, uint64_t bodies_bytes,
+                           const uint64_t *d_body_offsets, const uint32_t *d_body_lens,
+                           const uint16_t *d_reply_types, uint64_t n,
+                           const uint32_t *d_pending_ids, uint32_t npending,
+                           uint8_t *d_kind, uint32_t *d_id,
+                           uint32_t *d_result_off, uint32_t *d_result_len,
+                           uint32_t *d_error_off, uint32_t *d_error_len,
+                           uint32_t *d_slot, uint32_t *d_slot_entry,
+                           uint32_t *d_open, uint32_t *d_nopen, void *stream);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

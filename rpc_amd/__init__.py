@@ -93,6 +93,17 @@ __all__ = [
     "ROUTE_MAX_TOKENS",
     "ROUTE_MAX_METHODS",
     "ROUTE_MAX_METHOD_BYTES",
+    "frames_resolve",
+    "FrameResolve",
+    "RESOLVE_NONE",
+    "RESOLVE_MATCHED",
+    "RESOLVE_UNKNOWN",
+    "RESOLVE_DUPLICATE",
+    "RESOLVE_INVALID",
+    "RESOLVE_DEFER",
+    "RESOLVE_RANGE",
+    "RESOLVE_NO_SLOT",
+    "RESOLVE_MAX_PENDING",
     "frames_reply",
     "FrameReply",
     "REPLY_NONE",
@@ -144,6 +155,16 @@ ROUTE_MAX_DEPTH = 32
 ROUTE_MAX_TOKENS = 256
 ROUTE_MAX_METHODS = 256
 ROUTE_MAX_METHOD_BYTES = 4096
+# frames_resolve (include/rpccrc.h RPC_RESOLVE_*)
+RESOLVE_NONE = 0
+RESOLVE_MATCHED = 1
+RESOLVE_UNKNOWN = 2
+RESOLVE_DUPLICATE = 3
+RESOLVE_INVALID = 4
+RESOLVE_DEFER = 5
+RESOLVE_RANGE = 6
+RESOLVE_NO_SLOT = 0xFFFFFFFF
+RESOLVE_MAX_PENDING = 1 << 24
 # frames_reply (include/rpccrc.h RPC_REPLY_*)
 REPLY_NONE = 0
 REPLY_RESULT = 1
@@ -692,6 +713,65 @@ def frames_route(bodies, body_offsets, body_lens, table: RouteTable, reply_types
                                        first.data_ptr() if group else None, _stream_handle(stream)),
           "rpc_frames_route_device")
     return FrameRoute(kind, method, rid, poff, plen, order[:n] if group else None, first)
+
+
+class FrameResolve(NamedTuple):
+    """What frames_resolve returns (device tensors; nothing is read back)."""
+    kind: object        # uint8 [n]: RESOLVE_NONE / _MATCHED / _UNKNOWN / _DUPLICATE / _INVALID / _DEFER / _RANGE
+    id: object          # int32 [n]: the reply's id (view as uint32)
+    result_off: object  # int32 [n]: the `result` value, relative to the body's first byte ...
+    result_len: object  # int32 [n]: ... 0 / 0 when the reply has none
+    error_off: object   # int32 [n]: the `error` value likewise
+    error_len: object   # int32 [n]
+    slot: object        # int32 [n]: the pending slot a MATCHED / DUPLICATE entry names, else RESOLVE_NO_SLOT (-1)
+    slot_entry: object  # int32 [npending]: the entry that completes each slot, -1 while it stays open
+    open: object        # int32 [npending]: open[:nopen] lists the open slots, ascending
+    nopen: object       # int32 [1]
+
+
+def frames_resolve(bodies, body_offsets, body_lens, pending_ids=None, reply_types=None, stream=None) -> FrameResolve:
+    """The JSON-RPC reply envelope of every delivered body, matched to the pending calls
+    (rpc_frames_resolve_device): what sits between a client's ``frames_unpack`` and its
+    completions.
+
+    ``bodies, body_offsets, body_lens, reply_types`` are ``frames_unpack``'s outputs unchanged
+    (``reply_types=None``: every entry is DATA).  ``pending_ids[s]`` is the id of the call in the
+    caller's slot ``s`` (a 4-byte tensor; ``None`` or empty: decode only, every decoded entry
+    reads RESOLVE_UNKNOWN).  Per entry: the kind, the id, where the first top-level ``result``
+    and ``error`` values lie in the body, and the slot the reply answers; per slot: the entry
+    that completes it.  Bodies outside the strict subset of include/rpccrc.h read RESOLVE_DEFER:
+    parse those on the host as before."""
+    t = _torch()
+    n = body_offsets.numel()
+    for name, x, size, opt in (("body_offsets", body_offsets, 8, False), ("body_lens", body_lens, 4, False),
+                               ("reply_types", reply_types, 2, True)):
+        if x is None and opt:
+            continue
+        if x.numel() != n or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    if bodies.element_size() != 1 or not bodies.is_contiguous():
+        raise ValueError("bodies must be a contiguous uint8 tensor")
+    npending = 0 if pending_ids is None else pending_ids.numel()
+    if npending and (pending_ids.element_size() != 4 or not pending_ids.is_contiguous()):
+        raise ValueError("pending_ids must be a contiguous 4-byte tensor")
+    if npending > RESOLVE_MAX_PENDING:
+        raise ValueError(f"at most {RESOLVE_MAX_PENDING} pending ids")
+    dev = bodies.device
+    kind = t.empty(n, dtype=t.uint8, device=dev)
+    rid, roff, rlen, eoff, elen, slot = (t.empty(n, dtype=t.int32, device=dev) for _ in range(6))
+    slot_entry = t.empty(npending, dtype=t.int32, device=dev)
+    opened = t.empty(max(npending, 1), dtype=t.int32, device=dev)  # (never a null pointer)
+    nopen = t.empty(1, dtype=t.int32, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    check(_lib.rpc_frames_resolve_device(ptr(bodies), bodies.numel() if ptr(bodies) else 0, ptr(body_offsets),
+                                         ptr(body_lens), ptr(reply_types), n, ptr(pending_ids), npending, ptr(kind),
+                                         ptr(rid), ptr(roff), ptr(rlen), ptr(eoff), ptr(elen), ptr(slot),
+                                         ptr(slot_entry), opened.data_ptr(), nopen.data_ptr(), _stream_handle(stream)),
+          "rpc_frames_resolve_device")
+    return FrameResolve(kind, rid, roff, rlen, eoff, elen, slot, slot_entry, opened[:npending], nopen)
 
 
 class FrameReply(NamedTuple):

@@ -76,6 +76,8 @@ rpc_frames_carry_device = _sig("rpc_frames_carry_device", _i32, _vp, _u64, _vp, 
                                _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_route_device = _sig("rpc_frames_route_device", _i32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+rpc_frames_resolve_device = _sig("rpc_frames_resolve_device", _i32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_reply_device = _sig("rpc_frames_reply_device", _i32, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp,
                                _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_scan_device = _sig("rpc_frames_scan_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp, _u64, _vp, _vp, _vp,
@@ -128,6 +130,7 @@ EXPORTS = (
     "rpc_frames_unpack_device",
     "rpc_frames_carry_device",
     "rpc_frames_route_device",
+    "rpc_frames_resolve_device",
     "rpc_frames_reply_device",
     "rpc_frames_scan_device",
     "rpc_frames_scan_verify_device",

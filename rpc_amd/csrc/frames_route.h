@@ -11,6 +11,8 @@
 // route_method() then compares the method's raw bytes with the table.  Nothing
 // is converted but a digits-only id.  The caller applies rules 1 and 2
 // (route_precheck) before any byte is read.
+// Which depth-1 keys the walk records is a key policy (RouteKeys here; the frame
+// resolve walks replies with its own, frames_resolve.h).
 //
 // The grouping is a stable counting sort over buckets: route_bucket() names an
 // entry's bucket, route_wave_rank() is the rank inside one wave as the kernel
@@ -108,33 +110,58 @@ ROUTE_HD bool route_plain4(uint32_t x) {
   return ((below | ((q - ones) & ~q & high) | ((b - ones) & ~b & high))) == 0;
 }
 
-// What the walk recorded about the first depth-1 `id`, `method` and `params`.
+// What the walk recorded about the first depth-1 members 1, 2 and 3 of its key
+// policy (a request's `id`, `method` and `params`: RouteKeys below).
 struct RouteScan {
   bool strict;          // rules 3 and 4 hold, and rule 5 does not defer
   bool id_big;          // a digits-only id above 4294967295
-  bool has_method;      // the first `method` is a string
+  bool has_id;          // the first `id` is a number written as digits only
+  bool has_method;      // the first `method` is a string (kSpan2: member 2 is there)
   bool m_esc;           // ... with a backslash in it
   uint32_t id;          // rule 5 (0 when id_big)
-  uint32_t m_off, m_len; // the method's raw bytes
+  uint32_t m_off, m_len; // the method's raw bytes (kSpan2: member 2's value, as p_off / p_len)
   uint32_t p_off, p_len; // rule 8
+};
+
+// The key policy of a walk: key() names a depth-1 key of kl bytes at key_at as
+// member 1 (the id), 2, 3 or 0 (none); only the lengths it looks at cost a
+// compare.  Member 3's value is recorded as a span.  Member 2 is a string
+// whose raw bytes are recorded for a later compare, or with kSpan2 a second
+// span.  This one is a request's: `id`, `method`, `params`, compared exactly.
+struct RouteKeys {
+  static constexpr bool kSpan2 = false;
+  template <class Body> ROUTE_HD static uint32_t key(const Body &body, uint32_t key_at, uint32_t kl) {
+    if (kl == 2) {
+      if (body.at(key_at) == 'i' && body.at(key_at + 1) == 'd') return 1;
+    } else if (kl == 6) {
+      const uint32_t a = body.at(key_at) | (body.at(key_at + 1) << 8) | (body.at(key_at + 2) << 16) |
+                         (body.at(key_at + 3) << 24);
+      const uint32_t b = body.at(key_at + 4) | (body.at(key_at + 5) << 8);
+      if (a == 0x6874656Du && b == 0x646Fu) return 2; // "meth" "od"
+      if (a == 0x61726170u && b == 0x736Du) return 3; // "para" "ms"
+    }
+    return 0;
+  }
 };
 
 // Body: uint32_t next(), the body's bytes in order; bool aligned(), does the
 // next byte start a word of the staging area; uint32_t word(), that word (asked
 // only when aligned() and four bytes of the body are left); skip4(), step over
 // it; uint32_t at(uint32_t i), byte i again (i below the bytes handed out; used
-// for the few bytes of a depth-1 key of length 2 or 6 and for the compare).
-template <class Body> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len) {
-  RouteScan r{false, false, false, false, 0, 0, 0, 0, 0};
+// for the few bytes of a depth-1 key of a length the policy looks at and for
+// the compare).
+template <class Body, class Keys = RouteKeys> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len, Keys = Keys()) {
+  RouteScan r{false, false, false, false, false, 0, 0, 0, 0, 0};
   uint32_t state = kRsStart, depth = 0, stack = 0, tokens = 0, lit = 0;
   uint32_t key_at = 0;
-  uint32_t seen = 0; // bit 0 id, 1 method, 2 params: the key has occurred at depth 1
-  uint32_t want = 0; // the depth-1 value to come or under way: 1 id, 2 method, 3 params
+  uint32_t seen = 0; // bit 0 member 1, 1 member 2, 2 member 3: the key has occurred at depth 1
+  uint32_t want = 0; // the depth-1 value to come or under way: member 1, 2 or 3
   bool id_num = false;
   // A container closes at byte i: back to its parent, and a depth-1 value ends.
   const auto close = [&](uint32_t i) {
     --depth, stack >>= 1;
     if (depth == 1 && want == 3) r.p_len = i + 1 - r.p_off;
+    if (Keys::kSpan2 && depth == 1 && want == 2) r.m_len = i + 1 - r.m_off;
     if (depth == 1) want = 0;
     state = depth ? kRsAfter : kRsEnd;
   };
@@ -157,16 +184,7 @@ template <class Body> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len) {
         if (state == kRsKeyStr) {
           if (depth == 1) {
             const uint32_t kl = i - key_at;
-            uint32_t k = 0;
-            if (kl == 2) {
-              if (body.at(key_at) == 'i' && body.at(key_at + 1) == 'd') k = 1;
-            } else if (kl == 6) {
-              const uint32_t a = body.at(key_at) | (body.at(key_at + 1) << 8) | (body.at(key_at + 2) << 16) |
-                                 (body.at(key_at + 3) << 24);
-              const uint32_t b = body.at(key_at + 4) | (body.at(key_at + 5) << 8);
-              if (a == 0x6874656Du && b == 0x646Fu) k = 2; // "meth" "od"
-              if (a == 0x61726170u && b == 0x736Du) k = 3; // "para" "ms"
-            }
+            const uint32_t k = Keys::key(body, key_at, kl);
             want = 0;
             if (k && !((seen >> (k - 1)) & 1u)) { // the first wins
               seen |= 1u << (k - 1);
@@ -176,7 +194,7 @@ template <class Body> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len) {
           state = kRsColon;
         } else {
           if (depth == 1) {
-            if (want == 2) r.m_len = i - r.m_off;
+            if (want == 2) r.m_len = (Keys::kSpan2 ? i + 1 : i) - r.m_off;
             if (want == 3) r.p_len = i + 1 - r.p_off;
             want = 0;
           }
@@ -185,7 +203,7 @@ template <class Body> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len) {
       } else if (c == '\\') {
         if (depth == 1 && state == kRsKeyStr) return r; // rule 4
         // (rule 6 defers a method with a backslash, but after rule 5 has had its say)
-        if (depth == 1 && want == 2) r.m_esc = true;
+        if (!Keys::kSpan2 && depth == 1 && want == 2) r.m_esc = true;
         state = state == kRsKeyStr ? kRsKeyEsc : kRsStrEsc;
       } else if (c < 0x20) {
         return r;
@@ -203,6 +221,7 @@ template <class Body> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len) {
       if (!lit) {
         if (depth == 1) {
           if (want == 3) r.p_len = i + 1 - r.p_off;
+          if (Keys::kSpan2 && want == 2) r.m_len = i + 1 - r.m_off;
           want = 0;
         }
         state = kRsAfter;
@@ -252,6 +271,7 @@ template <class Body> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len) {
       }
       if (depth == 1) {
         if (want == 3) r.p_len = i - r.p_off;
+        if (Keys::kSpan2 && want == 2) r.m_len = i - r.m_off;
         want = 0;
       }
       id_num = false;
@@ -288,12 +308,13 @@ template <class Body> ROUTE_HD RouteScan route_scan(Body &body, uint32_t len) {
       if (depth == 1) { // the value of a depth-1 key begins
         if (want == 3) r.p_off = i;
         if (want == 2) {
-          if (c == '"') r.has_method = true, r.m_off = i + 1;
+          if (Keys::kSpan2) r.has_method = true, r.m_off = i;
+          else if (c == '"') r.has_method = true, r.m_off = i + 1;
           else want = 0;
         }
         if (want == 1) {
           if (c == '-') return r; // rule 5: a sign (a lone '-' is not strict either)
-          id_num = route_is_digit(c);
+          id_num = r.has_id = route_is_digit(c);
           want = 0;
         }
       }

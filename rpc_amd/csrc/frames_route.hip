@@ -8,6 +8,7 @@
 #include "../../include/rpccrc.h"
 #include "excl_scan.h"
 #include "frames_route.h"
+#include "frames_stage.h"
 
 namespace rpccrc {
 
@@ -24,30 +25,7 @@ namespace {
 
 constexpr int kRouteThreads = (int)kRouteEntries;
 constexpr uint32_t kRouteWaves = kRouteEntries / 64;
-constexpr uint32_t kNone32 = 0xFFFFFFFFu;
 
-// A staged body: the lane walks it word by word (one aligned LDS read per four
-// bytes; a byte read per byte at 64 unrelated addresses would be four times the
-// LDS instructions and their bank conflicts).
-struct LdsBody {
-  const uint32_t *lds;
-  uint32_t base; // byte offset of the body in the staging area
-  uint32_t pos = 0, w = 0;
-  __device__ __forceinline__ LdsBody(const uint32_t *l, uint32_t b) : lds(l), base(b) {}
-  __device__ __forceinline__ uint32_t next() {
-    const uint32_t p = base + pos;
-    if ((p & 3u) == 0 || pos == 0) w = lds[p >> 2];
-    ++pos;
-    return (w >> (8 * (p & 3u))) & 0xFFu;
-  }
-  __device__ __forceinline__ bool aligned() const { return ((base + pos) & 3u) == 0; }
-  __device__ __forceinline__ uint32_t word() const { return lds[(base + pos) >> 2]; }
-  __device__ __forceinline__ void skip4() { pos += 4; }
-  __device__ __forceinline__ uint32_t at(uint32_t i) const {
-    const uint32_t p = base + i;
-    return (lds[p >> 2] >> (8 * (p & 3u))) & 0xFFu;
-  }
-};
 struct LdsTab {
   const uint32_t *offs;
   const uint8_t *names;
@@ -64,20 +42,12 @@ __device__ __forceinline__ void put(const RouteArgs &a, uint64_t e, const RouteO
   if (a.bucket) a.bucket[e] = (uint16_t)route_bucket(o.kind, o.method, a.nmethods);
 }
 
-// One workgroup per kRouteEntries consecutive entries, one lane per entry.  The
-// bodies are staged in LDS in rounds: a round's window starts at the 16-byte
-// address step at or below the first pending body and takes every pending body
-// that lies inside its kRouteStage bytes (the unpack's bodies are back to back:
-// a run of consecutive entries; any other order still ends, a body per round at
-// the least).  Whole 16-byte blocks inside the buffer come with aligned
-// 16-byte loads, the edges that would leave [bodies, bodies + bodies_bytes)
-// bytewise.  Then each lane of the round walks its own body in LDS.
+// One workgroup per kRouteEntries consecutive entries, one lane per entry; the
+// bodies are staged in LDS in rounds (stage_rounds, frames_stage.h) and each
+// lane walks its own there.
 __global__ __launch_bounds__(kRouteThreads) void route_kernel(RouteArgs a) {
-  __shared__ uint4 s_stage[kRouteStage / 16];
   __shared__ uint32_t s_moff[kRouteMaxMethods + 1];
   __shared__ uint4 s_names[kRouteMaxMethodBytes / 16];
-  __shared__ uint64_t s_off[kRouteEntries];
-  __shared__ uint32_t s_first, s_end;
   const uint32_t t = threadIdx.x;
   const uint64_t e = (uint64_t)blockIdx.x * kRouteEntries + t;
 
@@ -101,46 +71,9 @@ __global__ __launch_bounds__(kRouteThreads) void route_kernel(RouteArgs a) {
     pending = route_precheck(has_type, type, off, len, a.bodies_bytes, &o);
     if (!pending) put(a, e, o);
   }
-  s_off[t] = off;
-  const uint64_t base_addr = (uint64_t)reinterpret_cast<uintptr_t>(a.bodies);
-  const uint32_t mis = (uint32_t)(base_addr & 15u);
   const LdsTab tab{s_moff, reinterpret_cast<const uint8_t *>(s_names)};
-  const uint32_t *stage32 = reinterpret_cast<const uint32_t *>(s_stage);
-
-  for (;;) {
-    if (t == 0) s_first = kNone32, s_end = 0;
-    __syncthreads(); // (also: s_off and the table are written; the last round's walks are over)
-    if (pending) atomicMin(&s_first, t);
-    __syncthreads();
-    const uint32_t first = s_first;
-    if (first == kNone32) break;
-    // the window in "aligned space": offsets from bodies - mis, so that a multiple
-    // of 16 there is a 16-byte address step
-    const uint64_t w0 = (s_off[first] + mis) & ~(uint64_t)15;
-    const uint64_t x0 = off + mis;
-    const bool mine = pending && x0 >= w0 && x0 + len <= w0 + kRouteStage;
-    if (mine) atomicMax(&s_end, (uint32_t)(x0 + len - w0));
-    __syncthreads();
-    const uint32_t blocks = (s_end + 15u) / 16u; // >= 1: the first pending body is in
-    const uint64_t lim = a.bodies_bytes + mis;   // the buffer is [mis, lim) in aligned space
-    for (uint32_t k = t; k < blocks; k += kRouteThreads) {
-      const uint64_t x = w0 + (uint64_t)k * 16u;
-      if (x >= mis && x + 16u <= lim) {
-        s_stage[k] = *reinterpret_cast<const uint4 *>(a.bodies + (x - mis));
-      } else { // the buffer's first or last block: only its bytes inside the buffer
-        uint32_t w[4] = {0, 0, 0, 0};
-        for (uint32_t b = 0; b < 16; ++b)
-          if (x + b >= mis && x + b < lim) w[b >> 2] |= (uint32_t)a.bodies[x + b - mis] << (8 * (b & 3u));
-        s_stage[k] = make_uint4(w[0], w[1], w[2], w[3]);
-      }
-    }
-    __syncthreads();
-    if (mine) {
-      LdsBody body(stage32, (uint32_t)(x0 - w0));
-      put(a, e, route_one(body, len, tab, a.nmethods, a.method_bytes));
-      pending = false;
-    }
-  }
+  stage_rounds(a.bodies, a.bodies_bytes, off, len, pending,
+               [&](LdsBody &body) { put(a, e, route_one(body, len, tab, a.nmethods, a.method_bytes)); });
 }
 
 // ---- groups: a stable counting sort over buckets x workgroups -------------------

@@ -39,6 +39,7 @@
 #include "frames_pack.h"
 #include "frames_scan.h"
 #include "frames_reply.h"
+#include "frames_resolve.h"
 #include "frames_route.h"
 #include "frames_unpack.h"
 
@@ -2228,6 +2229,61 @@ int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const i
   a.conn_bytes_first = d_conn_bytes_first;
   a.total = d_total;
   return map_hip(launch_frames_reply(a, s));
+}
+
+int rpc_frames_resolve_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
+                              const uint32_t *d_body_lens, const uint16_t *d_reply_types, uint64_t n,
+                              const uint32_t *d_pending_ids, uint32_t npending, uint8_t *d_kind, uint32_t *d_id,
+                              uint32_t *d_result_off, uint32_t *d_result_len, uint32_t *d_error_off,
+                              uint32_t *d_error_len, uint32_t *d_slot, uint32_t *d_slot_entry, uint32_t *d_open,
+                              uint32_t *d_nopen, void *stream) {
+  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (npending > RPC_RESOLVE_MAX_PENDING) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_body_offsets || !d_body_lens)) return RPCCRC_EINVAL;
+  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
+  if (npending > 0 && !d_pending_ids) return RPCCRC_EINVAL;
+  if ((d_open == nullptr) != (d_nopen == nullptr)) return RPCCRC_EINVAL;
+  if (n == 0 && !d_slot_entry && !d_nopen) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ResolveArgs a;
+  a.slot = d_slot;
+  a.slot_entry = d_slot_entry;
+  Lease wsl;
+  if (npending) { // (the decode-only call joins nothing)
+    a.bits = resolve_table_bits(npending);
+    const size_t tmp_words = d_open ? scan_tmp_words(npending) : 0;
+    rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+      if (d_open) {
+        a.flags = w.take<uint64_t>(npending);
+        a.offs = w.take<uint64_t>((uint64_t)npending + 1);
+        a.scan_tmp = w.take<uint64_t>(tmp_words);
+      }
+      a.cells = w.take<uint32_t>((uint64_t)1 << a.bits);
+      if (!d_slot_entry) a.slot_entry = w.take<uint32_t>(npending);
+      if (!d_slot && n) a.slot = w.take<uint32_t>(n);
+    });
+    if (rc) return rc;
+  }
+  a.bodies = d_bodies;
+  a.bodies_bytes = bodies_bytes;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.types = d_reply_types;
+  a.n = n;
+  a.pending = d_pending_ids;
+  a.npending = npending;
+  a.kind = d_kind;
+  a.id = d_id;
+  a.result_off = d_result_off;
+  a.result_len = d_result_len;
+  a.error_off = d_error_off;
+  a.error_len = d_error_len;
+  a.open = d_open;
+  a.nopen = d_nopen;
+  return map_hip(launch_frames_resolve(a, s));
 }
 
 int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
