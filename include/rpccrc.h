@@ -642,6 +642,94 @@ RPCCRC_API int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_
                            uint8_t *d_reply_status, uint64_t *d_conn_bytes_first, uint64_t *d_total,
                            void *stream);
 
+/* ---- frame request: JSON-RPC request bodies built from method + params + id ----
+ * The reply's mirror image: what sits in front of a client's pack.  Everything
+ * the reference client sends is one function (client/rpc_codec.c:6-20, printed
+ * by cJSON_PrintUnformatted):
+ *   {"jsonrpc":"2.0","method":"<name>","params":<params>,"id":<id>}
+ *   {"jsonrpc":"2.0","method":"<name>","id":<id>}                   (params == NULL)
+ * with <id> a uint32_t in plain decimal and the name through cJSON's string
+ * printer.  So a caller hands over a method index, the JSON text of its params
+ * and an id, and this call writes the envelope, lays the bodies out back to
+ * back and leaves the pack's inputs ready; the ids are
+ * rpc_frames_resolve_device's d_pending_ids.
+ * The method table is rpc_frames_route_device's (d_method_names, method_bytes,
+ * d_method_off, nmethods, with its two limits), so a client and a server share
+ * one table: d_method[i] is what the route would give back as the method index.
+ * d_types are the pack's types; NULL means every entry is DATA.  Entry i's
+ * value is d_params [d_params_offsets[i], + d_params_lens[i]).
+ * For entry i, in this order:
+ *   1. d_types is given and d_types[i] != RPC_FRAME_TYPE_DATA: size 0, type out
+ *      d_types[i] (a client's PING stays a PING for the pack, NONE stays NONE),
+ *      RPC_REQUEST_NONE.  Nothing else of the entry is looked at.
+ *   2. d_method[i] == RPC_ROUTE_NO_METHOD: the host built the whole request (a
+ *      notification without id, a name that needs escaping, anything outside
+ *      the form): the body is the value bytes verbatim, RPC_REQUEST_RAW.  An
+ *      empty value sends nothing: size 0, type NONE, RPC_REQUEST_NONE.  d_id is
+ *      not looked at.
+ *   3. RPC_REQUEST_BAD_METHOD, with size 0 and type NONE, if d_method[i] >=
+ *      nmethods; if the name's table word is not monotone (off[m] > off[m + 1])
+ *      or leaves method_bytes (rule 7 of the route: such a name matches nothing
+ *      there); or if the name holds a byte below 0x20, `"` or `\`: the
+ *      reference would print an escape there and the route compares raw bytes,
+ *      so such a name could not round-trip.  Bytes >= 0x80 are copied as they
+ *      are, as the reference does.  The empty name is legal.  Neither d_id nor
+ *      the value is looked at.
+ *   4. A value that rules 2 and 5 look at and that does not lie inside [0,
+ *      params_bytes) (offset <= params_bytes and length <= params_bytes -
+ *      offset, computed without 64-bit wrap; an empty value is held to it too),
+ *      or a body whose length would not fit 32 bits: size 0, type NONE,
+ *      RPC_REQUEST_RANGE.  Nothing is read.
+ *   5. Otherwise RPC_REQUEST_CALL.  With a non-empty value the first form above
+ *      around the value bytes, copied verbatim -- they are the caller's JSON
+ *      text; nothing is validated or escaped -- of 45 + name + value + digits
+ *      bytes.  With an empty value the second form, of 35 + name + digits bytes
+ *      (the reference's answer for params == NULL).  Id 0 is written like any
+ *      other (the reference's rpc_async_call refuses it; its server accepts it).
+ * Layout: d_body_offsets[i] is the exclusive 64-bit sum of the sizes of entries
+ * 0 .. i-1, d_body_lens[i] the size, *d_total the sum of all;
+ * d_conn_bytes_first[c] is the body offset of entry d_conn_first[c],
+ * d_conn_bytes_first[nconn] is *d_total (a CSR that runs past n reads as the
+ * end).  The layout never depends on out_cap.
+ * Capacity (the pack's rule): an entry of non-zero size that does not end
+ * inside out_cap is not written, not even in part; it reads RPC_REQUEST_NO_ROOM
+ * with type NONE; its offset and length keep the layout's values.  No byte of
+ * d_out outside a written entry is written.  d_out == NULL with out_cap == 0 is
+ * the layout-only call.
+ * Nothing outside [d_params, d_params + params_bytes) and the two table arrays
+ * is read, not even by an aligned load window.  d_out must not overlap
+ * d_params; d_types_out may be d_types.
+ * The outputs are rpc_frames_pack_device's inputs unchanged: bodies d_out,
+ * d_body_offsets, d_body_lens, types d_types_out (with the same d_conn_first).
+ * The length cap stays the pack's business (TOO_LARGE there).
+ * All pointers are device pointers; every output from d_body_offsets on is
+ * optional; the call is asynchronous on `stream`.
+ * RPCCRC_EINVAL, before any device is touched: n >= 0xFFFFFFFF; nmethods >
+ * RPC_ROUTE_MAX_METHODS; method_bytes > RPC_ROUTE_MAX_METHOD_BYTES; n > 0 with
+ * d_method, d_id, d_params_offsets or d_params_lens NULL; params_bytes > 0 with
+ * d_params NULL; nmethods > 0 with d_method_off NULL; method_bytes > 0 with
+ * d_method_names NULL; out_cap > 0 with d_out NULL; d_conn_bytes_first without
+ * d_conn_first; nconn > 0 with d_conn_first NULL.  n == 0 with neither d_total
+ * nor d_conn_bytes_first is RPCCRC_OK with no device; with them, *d_total and
+ * the nconn + 1 connection words are written as 0. */
+#define RPC_REQUEST_NONE 0u       /* nothing to send for this entry */
+#define RPC_REQUEST_CALL 1u       /* one of the two request forms */
+#define RPC_REQUEST_RAW 2u        /* the host's whole request, verbatim */
+#define RPC_REQUEST_BAD_METHOD 3u /* no such method, a broken table word, or a name that needs escaping */
+#define RPC_REQUEST_RANGE 4u      /* the value does not lie inside d_params, or the body is over 32 bits: nothing read */
+#define RPC_REQUEST_NO_ROOM 5u    /* the entry does not end inside out_cap: nothing written */
+RPCCRC_API int rpc_frames_request_device(const uint16_t *d_method, const uint32_t *d_id, const uint16_t *d_types,
+                           uint64_t n,
+                           const uint8_t *d_method_names, uint32_t method_bytes,
+                           const uint32_t *d_method_off, uint32_t nmethods,
+                           const uint8_t *d_params, uint64_t params_bytes,
+                           const uint64_t *d_params_offsets, const uint32_t *d_params_lens,
+                           const uint64_t *d_conn_first, uint64_t nconn,
+                           uint8_t *d_out, uint64_t out_cap,
+                           uint64_t *d_body_offsets, uint32_t *d_body_lens, uint16_t *d_types_out,
+                           uint8_t *d_request_status, uint64_t *d_conn_bytes_first, uint64_t *d_total,
+                           void *stream);
+
 /* ---- frame resolve: reply envelopes matched to pending ids -------------------
  * What sits between a client's unpack and its completions.  The reference
  * client parses each whole reply to learn its `id` and whether `result` or

@@ -112,6 +112,14 @@ __all__ = [
     "REPLY_RAW",
     "REPLY_RANGE",
     "REPLY_NO_ROOM",
+    "frames_request",
+    "FrameRequest",
+    "REQUEST_NONE",
+    "REQUEST_CALL",
+    "REQUEST_RAW",
+    "REQUEST_BAD_METHOD",
+    "REQUEST_RANGE",
+    "REQUEST_NO_ROOM",
 ]
 
 # reference rpc.h:11-17
@@ -172,6 +180,13 @@ REPLY_ERROR = 2
 REPLY_RAW = 3
 REPLY_RANGE = 4
 REPLY_NO_ROOM = 5
+# frames_request (include/rpccrc.h RPC_REQUEST_*)
+REQUEST_NONE = 0
+REQUEST_CALL = 1
+REQUEST_RAW = 2
+REQUEST_BAD_METHOD = 3
+REQUEST_RANGE = 4
+REQUEST_NO_ROOM = 5
 
 
 def _as_buffer(data) -> tuple[Optional[int], int, object]:
@@ -851,6 +866,87 @@ def frames_reply(kind, rid, values, value_offsets, value_lens, status=None, repl
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FrameReply(out, body_offsets, body_lens, types, state, cbf, nb)
+
+
+class FrameRequest(NamedTuple):
+    """What frames_request returns (device tensors; ``total`` is the host-side byte count, or with
+    a caller's ``out`` -- nothing is read back then -- a one-element int64 device tensor)."""
+    bodies: object            # uint8: the request bodies back to back
+    body_offsets: object      # int64 [n]: where each entry's body starts (entries of size 0 share the next one's)
+    body_lens: object         # int32 [n]: its length (view as uint32)
+    types: object             # int16 [n]: frames_pack's types: DATA / what types held / TYPE_NONE
+    status: object            # uint8 [n]: REQUEST_NONE / _CALL / _RAW / _BAD_METHOD / _RANGE / _NO_ROOM
+    conn_bytes_first: object  # int64 [nconn + 1], or None without conn_first
+    total: object             # bytes of all entries, whether they fitted or not
+
+
+def frames_request(method, rid, params, params_offsets, params_lens, table: RouteTable, types=None, conn_first=None,
+                   out=None, stream=None) -> FrameRequest:
+    """JSON-RPC request bodies from method + params + id (rpc_frames_request_device): what sits in
+    front of a client's ``frames_pack``.
+
+    ``method[i]`` indexes ``table`` (``route_table``: the server's table, so the index is what
+    ``frames_route`` gives back), ``rid[i]`` is the call's id -- the ids are ``frames_resolve``'s
+    ``pending_ids`` -- and entry i's params are ``params[params_offsets[i] : + params_lens[i]]``:
+    JSON text, wrapped as ``{"jsonrpc":"2.0","method":"<name>","params":<params>,"id":<id>}``, or
+    without the ``params`` member when empty.  ``method[i] == ROUTE_NO_METHOD`` copies the bytes
+    verbatim: a whole request the host built.  ``types`` are ``frames_pack``'s (``None``: every
+    entry is DATA); an entry of another type has no body and keeps its type.  ``bodies,
+    body_offsets, body_lens, types`` go to ``frames_pack`` unchanged, with the same ``conn_first``.
+
+    ``out=None`` makes the layout-only call first, reads the total (one synchronisation),
+    allocates exactly and builds.  With ``out`` (a contiguous uint8 device tensor that does not
+    overlap ``params``) nothing is read back: entries that do not end inside it are
+    REQUEST_NO_ROOM / TYPE_NONE and not written, and ``total`` stays on the device."""
+    t = _torch()
+    n = rid.numel()
+    for name, x, size, opt in (("method", method, 2, False), ("rid", rid, 4, False), ("types", types, 2, True),
+                               ("params_offsets", params_offsets, 8, False), ("params_lens", params_lens, 4, False)):
+        if x is None and opt:
+            continue
+        if x.numel() != n or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    if params.element_size() != 1 or not params.is_contiguous():
+        raise ValueError("params must be a contiguous uint8 tensor")
+    if table.offsets.numel() != table.nmethods + 1 or table.offsets.element_size() != 4:
+        raise ValueError("table.offsets needs nmethods + 1 4-byte entries")
+    if conn_first is not None and (conn_first.numel() < 1 or conn_first.element_size() != 8):
+        raise ValueError("conn_first needs nconn + 1 8-byte entries")
+    if out is not None and (out.element_size() != 1 or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 tensor")
+    dev = rid.device
+    nconn = 0 if conn_first is None else conn_first.numel() - 1
+    sh = _stream_handle(stream)
+    body_offsets = t.empty(n, dtype=t.int64, device=dev)
+    body_lens = t.empty(n, dtype=t.int32, device=dev)
+    types_out = t.empty(n, dtype=t.int16, device=dev)
+    state = t.empty(n, dtype=t.uint8, device=dev)
+    cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
+    total = t.zeros(1, dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    def run(dst, layout_only):
+        outs = (None,) * 5 if layout_only else (ptr(body_offsets), ptr(body_lens), ptr(types_out), ptr(state), ptr(cbf))
+        check(_lib.rpc_frames_request_device(ptr(method), ptr(rid), ptr(types), n, ptr(table.names),
+                                             table.names.numel(), ptr(table.offsets), table.nmethods, ptr(params),
+                                             params.numel() if ptr(params) else 0, ptr(params_offsets),
+                                             ptr(params_lens), None if conn_first is None else conn_first.data_ptr(),
+                                             nconn, ptr(dst), 0 if dst is None else dst.numel(), *outs,
+                                             total.data_ptr(), sh),
+              "rpc_frames_request_device")
+
+    if out is not None:
+        run(out, False)
+        return FrameRequest(out, body_offsets, body_lens, types_out, state, cbf, total)
+    run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
+    if stream is not None:
+        stream.synchronize()
+    nb = int(total.cpu()[0])
+    out = t.empty(nb, dtype=t.uint8, device=dev)
+    run(out, False)
+    return FrameRequest(out, body_offsets, body_lens, types_out, state, cbf, nb)
 
 
 class FrameScan(NamedTuple):

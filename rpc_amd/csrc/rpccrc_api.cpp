@@ -39,6 +39,7 @@
 #include "frames_pack.h"
 #include "frames_scan.h"
 #include "frames_reply.h"
+#include "frames_request.h"
 #include "frames_resolve.h"
 #include "frames_route.h"
 #include "frames_unpack.h"
@@ -2229,6 +2230,62 @@ int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const i
   a.conn_bytes_first = d_conn_bytes_first;
   a.total = d_total;
   return map_hip(launch_frames_reply(a, s));
+}
+
+int rpc_frames_request_device(const uint16_t *d_method, const uint32_t *d_id, const uint16_t *d_types, uint64_t n,
+                              const uint8_t *d_method_names, uint32_t method_bytes, const uint32_t *d_method_off,
+                              uint32_t nmethods, const uint8_t *d_params, uint64_t params_bytes,
+                              const uint64_t *d_params_offsets, const uint32_t *d_params_lens,
+                              const uint64_t *d_conn_first, uint64_t nconn, uint8_t *d_out, uint64_t out_cap,
+                              uint64_t *d_body_offsets, uint32_t *d_body_lens, uint16_t *d_types_out,
+                              uint8_t *d_request_status, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
+  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
+  if (nmethods > RPC_ROUTE_MAX_METHODS || method_bytes > RPC_ROUTE_MAX_METHOD_BYTES) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_method || !d_id || !d_params_offsets || !d_params_lens)) return RPCCRC_EINVAL;
+  if (params_bytes > 0 && !d_params) return RPCCRC_EINVAL;
+  if (nmethods > 0 && !d_method_off) return RPCCRC_EINVAL;
+  if (method_bytes > 0 && !d_method_names) return RPCCRC_EINVAL;
+  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
+  RequestArgs a;
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    const RequestWs ws = request_ws_layout(w, n, scan_tmp_words(n));
+    a.sizes = ws.sizes;
+    a.src_off = ws.src_off;
+    a.offs = ws.offs;
+    a.scan_tmp = ws.scan_tmp;
+    a.meta = ws.meta;
+    a.name_word = ws.name_word;
+  });
+  if (rc) return rc;
+  a.method = d_method;
+  a.id = d_id;
+  a.types = d_types;
+  a.n = n;
+  a.names = d_method_names;
+  a.method_bytes = method_bytes;
+  a.method_off = d_method_off;
+  a.nmethods = nmethods;
+  a.params = d_params;
+  a.params_bytes = params_bytes;
+  a.params_off = d_params_offsets;
+  a.params_len = d_params_lens;
+  a.conn_first = d_conn_first;
+  a.nconn = nconn;
+  a.out = d_out;
+  a.out_cap = out_cap;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.types_out = d_types_out;
+  a.request_status = d_request_status;
+  a.conn_bytes_first = d_conn_bytes_first;
+  a.total = d_total;
+  return map_hip(launch_frames_request(a, s));
 }
 
 int rpc_frames_resolve_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
