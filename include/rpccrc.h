@@ -812,6 +812,120 @@ RPCCRC_API int rpc_frames_resolve_device(const uint8_t *d_bodies, uint64_t bodie
                            uint32_t *d_slot, uint32_t *d_slot_entry,
                            uint32_t *d_open, uint32_t *d_nopen, void *stream);
 
+/* ---- frame args: typed params decoded per method schema ----------------------
+ * What sits between the route and the handlers.  The reference's generated
+ * rpc_parse_params_<method> functions (rpc_server_skeleton.c:13-116,
+ * rpc_parse_i64_value in rpc_server_helpers.c:56-75) look a fixed list of
+ * (name, type) up in the flat `params` object by case-sensitive name; there
+ * are five types.  This call does that for every CALL entry of a route: it
+ * decodes the method's declared parameters into typed 64-bit slots, column by
+ * column, so that a handler runs once over arrays of numbers and the -32602
+ * answers are decided without the host seeing them.  Like the route it is not
+ * a JSON codec: it accepts a strict subset, inside the subset its answer is
+ * the reference's, and everything else reads RPC_ARGS_DEFER and goes through
+ * the host's parser on the span as before.
+ * d_bodies, d_body_offsets, d_body_lens are the unpack's outputs; d_kind,
+ * d_method, d_params_off, d_params_len the route's, all unchanged.  The schema:
+ * method m declares parameters [d_param_first[m], d_param_first[m + 1]) (a CSR
+ * of nmethods + 1 words, in the order of the route's table); parameter p has
+ * type d_param_types[p] (RPC_ARG_*) and the name bytes [d_param_name_off[p],
+ * d_param_name_off[p + 1]) of d_param_names.  `width` is the slots per entry.
+ * For entry i, in this order:
+ *   1. d_kind[i] != RPC_ROUTE_CALL: RPC_ARGS_NONE.  Nothing else of the entry
+ *      is looked at.
+ *   2. RPC_ARGS_BAD_SCHEMA, with no body byte read, if d_method[i] >= nmethods;
+ *      if the method's two CSR words are not monotone or leave nparams; if the
+ *      method has more than `width` parameters; if one of its parameters has an
+ *      unknown type code or name words that are not monotone or leave
+ *      name_bytes.  (Only the entry's own method is looked at.)
+ *   3. RPC_ARGS_RANGE, with nothing read, if the body does not lie inside
+ *      [0, bodies_bytes) or the span does not lie inside the body (both
+ *      computed without wrap).
+ *   4. The method declares no parameters: RPC_ARGS_OK, and the span is not
+ *      read (the reference's `ping` takes any params, absent ones included).
+ *   5. d_params_len[i] == 0: RPC_ARGS_INVALID (the reference substitutes {} and
+ *      every lookup fails).
+ *   6. RPC_ARGS_DEFER unless the span is one strict JSON value -- an object,
+ *      array, string, number or literal by the grammar of the route's rule 3,
+ *      with no byte, whitespace included, before or after the value -- of at
+ *      most RPC_ROUTE_MAX_BODY bytes, nested no deeper than
+ *      RPC_ROUTE_MAX_DEPTH - 1 (the span's outermost container is depth 1) and
+ *      with at most RPC_ROUTE_MAX_TOKENS tokens, counted as the route counts.
+ *   7. A strict value that is not an object: RPC_ARGS_INVALID ([1,2] and null
+ *      answer -32602 in the reference).
+ *   8. RPC_ARGS_DEFER if a depth-1 key of the object contains a backslash.
+ *      Keys are compared as raw bytes, case-sensitively, and the FIRST equal
+ *      key wins: {"a":1,"a":5} reads 1, {"A":1,"a":3} reads 3.  Other keys and
+ *      anything nested are skipped.  Two parameters of one name read the same
+ *      value; the empty name is legal.
+ *   9. RPC_ARGS_INVALID if a declared parameter is absent or its value is of a
+ *      JSON type its declared type does not take, judged from the value's
+ *      first byte alone, before any conversion (so INVALID wins over DEFER, as
+ *      in the reference): a number takes I32, I64, F64; true / false takes
+ *      BOOL only; a string takes STR and I64; null, an object and an array
+ *      take none.
+ *  10. Otherwise each parameter is converted; RPC_ARGS_DEFER if a conversion
+ *      leaves the subset, else RPC_ARGS_OK:
+ *      F64   the bit pattern of the double strtod gives, correctly rounded.
+ *            In the subset: at most 19 significant digits once leading zeros
+ *            are stripped (trailing zeros count), and a result that is zero
+ *            because every digit is 0 (the sign is kept: -0.0 is
+ *            0x8000000000000000) or a normal double.  DEFER: more digits, a
+ *            non-zero number whose double is zero, subnormal or infinite.
+ *      I32   with d the F64 conversion: (int64_t)trunc(d) when -2147483649 < d
+ *            < 2147483648 (the reference's (int32_t)valuedouble: 1.9 -> 1,
+ *            -1.9 -> -1, 1e3 -> 1000), else DEFER (the cast is undefined there).
+ *      I64   from a number: (int64_t)trunc(d) when -2^63 <= d < 2^63, else
+ *            DEFER (9007199254740993 reads ...992, through the double, as in
+ *            the reference).  From a string, the reference's strtoll path and
+ *            what its client sends: -?[0-9]{1,19} with a value inside int64
+ *            gives that value; every other string is DEFER (the host runs
+ *            strtoll: blanks and '+' are accepted there, "12a" and "" are
+ *            -32602, an overflow saturates).
+ *      BOOL  1 or 0.
+ *      STR   offset | (uint64_t)length << 32 of the bytes between the quotes,
+ *            the offset relative to the body's first byte.  A backslash
+ *            inside is DEFER: the host unescapes.
+ * d_slots (width * n words) holds slot k of entry i at k * n + i, column-major:
+ * for OK the method's parameters in declaration order and 0 behind them, for
+ * every other status `width` zeros.  d_status is the RPC_ARGS_* above;
+ * d_reply_status is 0 for OK, -32602 for INVALID and -32603 for everything
+ * else, and goes to rpc_frames_reply_device as its d_status (the host
+ * overwrites it for the DEFER entries it handles; an entry nobody handled
+ * answers "Internal error", never an empty result).
+ * Nothing outside [d_bodies, d_bodies + bodies_bytes) and the schema arrays is
+ * read, not even by an aligned load window.  All pointers are device pointers;
+ * every output is optional; the call is asynchronous on `stream`.
+ * RPCCRC_EINVAL, before any device is touched: n >= 0xFFFFFFFF; nmethods >
+ * RPC_ROUTE_MAX_METHODS; nparams > RPC_ARGS_MAX_SCHEMA_PARAMS; name_bytes >
+ * RPC_ARGS_MAX_NAME_BYTES; width 0 or > RPC_ARGS_MAX_PARAMS; n > 0 with
+ * d_body_offsets, d_body_lens, d_kind, d_method, d_params_off or d_params_len
+ * NULL; bodies_bytes > 0 with d_bodies NULL; nmethods > 0 with d_param_first
+ * NULL; nparams > 0 with d_param_types or d_param_name_off NULL; name_bytes > 0
+ * with d_param_names NULL.  n == 0 is RPCCRC_OK with no device touched. */
+#define RPC_ARGS_NONE 0u       /* not a CALL entry: nothing to decode */
+#define RPC_ARGS_OK 1u         /* every declared parameter decoded */
+#define RPC_ARGS_INVALID 2u    /* a parameter absent or of the wrong JSON type (-32602) */
+#define RPC_ARGS_DEFER 3u      /* outside the strict subset: the host's parser decides */
+#define RPC_ARGS_RANGE 4u      /* the body or the span lies outside its buffer: nothing read */
+#define RPC_ARGS_BAD_SCHEMA 5u /* the method's schema words are broken: no body byte read */
+#define RPC_ARG_I32 0u
+#define RPC_ARG_I64 1u
+#define RPC_ARG_F64 2u
+#define RPC_ARG_BOOL 3u
+#define RPC_ARG_STR 4u
+#define RPC_ARGS_MAX_PARAMS 8u
+#define RPC_ARGS_MAX_SCHEMA_PARAMS 1024u
+#define RPC_ARGS_MAX_NAME_BYTES 4096u
+RPCCRC_API int rpc_frames_args_device(const uint8_t *d_bodies, uint64_t bodies_bytes,
+                           const uint64_t *d_body_offsets, const uint32_t *d_body_lens,
+                           const uint8_t *d_kind, const uint16_t *d_method,
+                           const uint32_t *d_params_off, const uint32_t *d_params_len, uint64_t n,
+                           const uint32_t *d_param_first, uint32_t nmethods,
+                           const uint8_t *d_param_types, const uint32_t *d_param_name_off, uint32_t nparams,
+                           const uint8_t *d_param_names, uint32_t name_bytes, uint32_t width,
+                           uint64_t *d_slots, uint8_t *d_status, int32_t *d_reply_status, void *stream);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

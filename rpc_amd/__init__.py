@@ -93,6 +93,24 @@ __all__ = [
     "ROUTE_MAX_TOKENS",
     "ROUTE_MAX_METHODS",
     "ROUTE_MAX_METHOD_BYTES",
+    "frames_args",
+    "FrameArgs",
+    "args_schema",
+    "ArgsSchema",
+    "ARGS_NONE",
+    "ARGS_OK",
+    "ARGS_INVALID",
+    "ARGS_DEFER",
+    "ARGS_RANGE",
+    "ARGS_BAD_SCHEMA",
+    "ARG_I32",
+    "ARG_I64",
+    "ARG_F64",
+    "ARG_BOOL",
+    "ARG_STR",
+    "ARGS_MAX_PARAMS",
+    "ARGS_MAX_SCHEMA_PARAMS",
+    "ARGS_MAX_NAME_BYTES",
     "frames_resolve",
     "FrameResolve",
     "RESOLVE_NONE",
@@ -163,6 +181,21 @@ ROUTE_MAX_DEPTH = 32
 ROUTE_MAX_TOKENS = 256
 ROUTE_MAX_METHODS = 256
 ROUTE_MAX_METHOD_BYTES = 4096
+# frames_args (include/rpccrc.h RPC_ARGS_* / RPC_ARG_*)
+ARGS_NONE = 0
+ARGS_OK = 1
+ARGS_INVALID = 2
+ARGS_DEFER = 3
+ARGS_RANGE = 4
+ARGS_BAD_SCHEMA = 5
+ARG_I32 = 0
+ARG_I64 = 1
+ARG_F64 = 2
+ARG_BOOL = 3
+ARG_STR = 4
+ARGS_MAX_PARAMS = 8
+ARGS_MAX_SCHEMA_PARAMS = 1024
+ARGS_MAX_NAME_BYTES = 4096
 # frames_resolve (include/rpccrc.h RPC_RESOLVE_*)
 RESOLVE_NONE = 0
 RESOLVE_MATCHED = 1
@@ -728,6 +761,98 @@ def frames_route(bodies, body_offsets, body_lens, table: RouteTable, reply_types
                                        first.data_ptr() if group else None, _stream_handle(stream)),
           "rpc_frames_route_device")
     return FrameRoute(kind, method, rid, poff, plen, order[:n] if group else None, first)
+
+
+class ArgsSchema(NamedTuple):
+    """A server's parameter schema on the device (args_schema)."""
+    first: object     # int32 [nmethods + 1]: method m declares parameters first[m] : first[m + 1]
+    types: object     # uint8 [nparams]: ARG_I32 / _I64 / _F64 / _BOOL / _STR
+    name_off: object  # int32 [nparams + 1]: parameter p is called names[name_off[p] : name_off[p + 1]]
+    names: object     # uint8: the parameter names back to back
+    nmethods: int
+    nparams: int
+    width: int        # the most parameters any method declares (at least 1)
+
+
+_ARG_TYPES = {"i32": ARG_I32, "i64": ARG_I64, "double": ARG_F64, "f64": ARG_F64, "bool": ARG_BOOL, "string": ARG_STR,
+              "str": ARG_STR}
+
+
+def args_schema(methods, device=None) -> ArgsSchema:
+    """The schema tensors of frames_args from ``[(name, [(param, type), ...]), ...]`` in the order
+    of ``route_table`` (one list builds both: ``route_table(m for m, _ in methods)``).  A type is
+    an ``ARG_*`` constant or one of the IDL's names: i32, i64, double, bool, string."""
+    t = _torch()
+    first, types, noff, names = [0], [], [0], bytearray()
+    for _, params in methods:
+        if len(params) > ARGS_MAX_PARAMS:
+            raise ValueError(f"at most {ARGS_MAX_PARAMS} parameters per method")
+        for pname, ptype in params:
+            types.append(_ARG_TYPES[ptype] if isinstance(ptype, str) else int(ptype))
+            names += pname.encode() if isinstance(pname, str) else bytes(pname)
+            noff.append(len(names))
+        first.append(len(types))
+    if len(first) - 1 > ROUTE_MAX_METHODS or len(types) > ARGS_MAX_SCHEMA_PARAMS or len(names) > ARGS_MAX_NAME_BYTES:
+        raise ValueError(f"at most {ROUTE_MAX_METHODS} methods, {ARGS_MAX_SCHEMA_PARAMS} parameters and "
+                         f"{ARGS_MAX_NAME_BYTES} bytes of names")
+    dev = "cuda" if device is None else device
+    width = max([1] + [b - a for a, b in zip(first, first[1:])])
+    return ArgsSchema(t.tensor(first, dtype=t.int32).to(dev), t.tensor(types, dtype=t.uint8).to(dev),
+                      t.tensor(noff, dtype=t.int32).to(dev), t.tensor(list(names), dtype=t.uint8).to(dev),
+                      len(first) - 1, len(types), width)
+
+
+class FrameArgs(NamedTuple):
+    """What frames_args returns (device tensors; nothing is read back)."""
+    status: object        # uint8 [n]: ARGS_NONE / _OK / _INVALID / _DEFER / _RANGE / _BAD_SCHEMA
+    reply_status: object  # int32 [n]: 0, -32602 (INVALID) or -32603: frames_reply's ``status``
+    slots: object         # int64 [width, n]: slots[k] is parameter k's column (F64: .view(torch.float64))
+
+
+def frames_args(bodies, body_offsets, body_lens, route: FrameRoute, schema: ArgsSchema, width: Optional[int] = None,
+                stream=None) -> FrameArgs:
+    """The declared parameters of every routed request as typed 64-bit slots
+    (rpc_frames_args_device): what sits between ``frames_route`` and the handlers.
+
+    ``bodies, body_offsets, body_lens`` are ``frames_unpack``'s outputs and ``route`` is
+    ``frames_route``'s, all unchanged; ``schema`` (``args_schema``) lists each method's
+    parameters in the order of the route's table.  Per CALL entry the method's parameters are
+    looked up by name in the ``params`` object and converted column by column: an I32 / I64 /
+    BOOL slot is the value, an F64 slot the double's bits, a STR slot ``offset | length << 32``
+    of the bytes between the quotes, relative to the body's first byte.  ARGS_INVALID entries
+    answer -32602 without the host looking at them; spans outside the strict subset of
+    include/rpccrc.h read ARGS_DEFER: parse those on the host as before (``json.loads`` on the
+    span) and overwrite their ``reply_status``.  ``width`` (default ``schema.width``) is the
+    number of slot columns."""
+    t = _torch()
+    n = body_offsets.numel()
+    for name, x, size in (("body_offsets", body_offsets, 8), ("body_lens", body_lens, 4), ("route.kind", route.kind, 1),
+                          ("route.method", route.method, 2), ("route.params_off", route.params_off, 4),
+                          ("route.params_len", route.params_len, 4)):
+        if x.numel() != n or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    if bodies.element_size() != 1 or not bodies.is_contiguous():
+        raise ValueError("bodies must be a contiguous uint8 tensor")
+    if (schema.first.numel() != schema.nmethods + 1 or schema.types.numel() != schema.nparams or
+            schema.name_off.numel() != schema.nparams + 1 or schema.first.element_size() != 4 or
+            schema.types.element_size() != 1 or schema.name_off.element_size() != 4):
+        raise ValueError("schema needs nmethods + 1 4-byte CSR words, nparams types and nparams + 1 4-byte name words")
+    width = schema.width if width is None else int(width)
+    dev = bodies.device
+    status = t.empty(n, dtype=t.uint8, device=dev)
+    reply_status = t.empty(n, dtype=t.int32, device=dev)
+    slots = t.empty((width if 1 <= width <= ARGS_MAX_PARAMS else 0, n), dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    check(_lib.rpc_frames_args_device(ptr(bodies), bodies.numel() if ptr(bodies) else 0, ptr(body_offsets),
+                                      ptr(body_lens), ptr(route.kind), ptr(route.method), ptr(route.params_off),
+                                      ptr(route.params_len), n, ptr(schema.first), schema.nmethods, ptr(schema.types),
+                                      ptr(schema.name_off), schema.nparams, ptr(schema.names), schema.names.numel(),
+                                      width, ptr(slots), ptr(status), ptr(reply_status), _stream_handle(stream)),
+          "rpc_frames_args_device")
+    return FrameArgs(status, reply_status, slots)
 
 
 class FrameResolve(NamedTuple):

@@ -1,8 +1,9 @@
 // rpc_amd/csrc/frames_stage.h -- the staging rounds of the walks over delivered
-// bodies, shared by the frame route and the frame resolve (frames_route.hip,
-// frames_resolve.hip): a workgroup of kRouteEntries lanes, one
-// entry each, brings its bodies into LDS in rounds of kRouteStage bytes and
-// each lane walks its own body there through an LdsBody.
+// bodies, shared by the frame route, the frame resolve and the frame args
+// (frames_route.hip, frames_resolve.hip, frames_args.hip): a
+// workgroup of kRouteEntries lanes, one entry each, brings its bodies (the
+// args: its `params` spans) into LDS in rounds of kRouteStage bytes and each
+// lane walks its own there through an LdsBody.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

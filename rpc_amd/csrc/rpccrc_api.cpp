@@ -35,6 +35,7 @@
 #include "crc32_layout.h"
 #include "crc32_service_math.h"
 #include "frames.h"
+#include "frames_args.h"
 #include "frames_carry.h"
 #include "frames_pack.h"
 #include "frames_scan.h"
@@ -2181,6 +2182,51 @@ int rpc_frames_route_device(const uint8_t *d_bodies, uint64_t bodies_bytes, cons
   a.order = d_order;
   a.group_first = d_group_first;
   return map_hip(launch_frames_route(a, s));
+}
+
+int rpc_frames_args_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
+                           const uint32_t *d_body_lens, const uint8_t *d_kind, const uint16_t *d_method,
+                           const uint32_t *d_params_off, const uint32_t *d_params_len, uint64_t n,
+                           const uint32_t *d_param_first, uint32_t nmethods, const uint8_t *d_param_types,
+                           const uint32_t *d_param_name_off, uint32_t nparams, const uint8_t *d_param_names,
+                           uint32_t name_bytes, uint32_t width, uint64_t *d_slots, uint8_t *d_status,
+                           int32_t *d_reply_status, void *stream) {
+  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (nmethods > RPC_ROUTE_MAX_METHODS || nparams > RPC_ARGS_MAX_SCHEMA_PARAMS || name_bytes > RPC_ARGS_MAX_NAME_BYTES)
+    return RPCCRC_EINVAL;
+  if (width == 0 || width > RPC_ARGS_MAX_PARAMS) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_body_offsets || !d_body_lens || !d_kind || !d_method || !d_params_off || !d_params_len))
+    return RPCCRC_EINVAL;
+  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
+  if (nmethods > 0 && !d_param_first) return RPCCRC_EINVAL;
+  if (nparams > 0 && (!d_param_types || !d_param_name_off)) return RPCCRC_EINVAL;
+  if (name_bytes > 0 && !d_param_names) return RPCCRC_EINVAL;
+  if (n == 0) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  const int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  ArgsArgs a;
+  a.bodies = d_bodies;
+  a.bodies_bytes = bodies_bytes;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.kind = d_kind;
+  a.method = d_method;
+  a.params_off = d_params_off;
+  a.params_len = d_params_len;
+  a.n = n;
+  a.param_first = d_param_first;
+  a.nmethods = nmethods;
+  a.param_types = d_param_types;
+  a.param_name_off = d_param_name_off;
+  a.nparams = nparams;
+  a.param_names = d_param_names;
+  a.name_bytes = name_bytes;
+  a.width = width;
+  a.slots = d_slots;
+  a.status = d_status;
+  a.reply_status = d_reply_status;
+  return map_hip(launch_frames_args(a, static_cast<hipStream_t>(stream)));
 }
 
 int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const int32_t *d_status,
