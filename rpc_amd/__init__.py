@@ -336,10 +336,32 @@ def _torch():
     return _lib.torch
 
 
+# The stream contract of every device-buffer call below.  ``stream=None`` is torch's current
+# stream.  ``stream=s`` alone is enough: every launch, memset and copy of the call -- the
+# library's and the wrapper's own, a read-back included -- goes to ``s`` and to no other stream,
+# whatever torch's current stream is and however busy it is; the wrapper allocates (``t.empty``,
+# no fill) and does nothing else on the device.  What the caller owes: the inputs are ready in
+# ``s``'s order, and the tensors handed in and returned stay alive until ``s`` has run the call
+# (torch's allocator knows the current stream only).  ``s`` is a ``torch.cuda.Stream`` or any
+# object whose ``cuda_stream`` is a ``hipStream_t``; the variants that read a count or a total
+# back (``out=None``; ``frames_scan`` unless ``read_count=False``) copy it on ``s`` and wait
+# for ``s`` alone.
+
 def _stream_handle(stream) -> int:
     t = _torch()
     s = stream if stream is not None else t.cuda.current_stream()
     return int(s.cuda_stream)
+
+
+def _read_back(x, stream) -> int:
+    """x[0] on the host, copied on the call's stream: that stream is synchronised, no other."""
+    t = _torch()
+    if stream is None:
+        return int(x.cpu()[0])
+    own = stream if isinstance(stream, t.cuda.Stream) else t.cuda.ExternalStream(int(stream.cuda_stream),
+                                                                                 device=x.device)
+    with t.cuda.stream(own):
+        return int(x.cpu()[0])
 
 
 def _dev_u32_out(n: int, device, out):
@@ -514,7 +536,7 @@ def frames_pack(bodies, body_offsets, body_lens, types=None, version: int = 1, t
     verdict = t.empty(n, dtype=t.uint8, device=dev)
     crc = t.empty(n, dtype=t.int32, device=dev)
     cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
-    total = t.zeros(1, dtype=t.int64, device=dev)
+    total = t.empty(1, dtype=t.int64, device=dev)  # (the call always writes it)
 
     def ptr(x):
         return None if x is None or x.numel() == 0 else x.data_ptr()
@@ -532,9 +554,7 @@ def frames_pack(bodies, body_offsets, body_lens, types=None, version: int = 1, t
         run(out, False)
         return FramePack(out, offsets, verdict, crc, cbf, total)
     run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
-    if stream is not None:
-        stream.synchronize()
-    nb = int(total.cpu()[0])
+    nb = _read_back(total, stream)
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FramePack(out, offsets, verdict, crc, cbf, nb)
@@ -591,7 +611,7 @@ def frames_unpack(stream_buf, frame_offsets, verdict, role: str = "server", lift
     versions = t.empty(n, dtype=t.int16, device=dev)
     verdict_out = t.empty(n, dtype=t.uint8, device=dev)
     cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
-    total = t.zeros(1, dtype=t.int64, device=dev)
+    total = t.empty(1, dtype=t.int64, device=dev)  # (the call always writes it)
 
     def ptr(x):
         return None if x is None or x.numel() == 0 else x.data_ptr()
@@ -608,9 +628,7 @@ def frames_unpack(stream_buf, frame_offsets, verdict, role: str = "server", lift
         run(out, False)
         return FrameUnpack(out, body_offsets, body_lens, reply_types, versions, verdict_out, cbf, total)
     run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
-    if stream is not None:
-        stream.synchronize()
-    nb = int(total.cpu()[0])
+    nb = _read_back(total, stream)
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FrameUnpack(out, body_offsets, body_lens, reply_types, versions, verdict_out, cbf, nb)
@@ -968,7 +986,7 @@ def frames_reply(kind, rid, values, value_offsets, value_lens, status=None, repl
     types = t.empty(n, dtype=t.int16, device=dev)
     state = t.empty(n, dtype=t.uint8, device=dev)
     cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
-    total = t.zeros(1, dtype=t.int64, device=dev)
+    total = t.empty(1, dtype=t.int64, device=dev)  # (the call always writes it)
 
     def ptr(x):
         return None if x is None or x.numel() == 0 else x.data_ptr()
@@ -985,9 +1003,7 @@ def frames_reply(kind, rid, values, value_offsets, value_lens, status=None, repl
         run(out, False)
         return FrameReply(out, body_offsets, body_lens, types, state, cbf, total)
     run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
-    if stream is not None:
-        stream.synchronize()
-    nb = int(total.cpu()[0])
+    nb = _read_back(total, stream)
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FrameReply(out, body_offsets, body_lens, types, state, cbf, nb)
@@ -1047,7 +1063,7 @@ def frames_request(method, rid, params, params_offsets, params_lens, table: Rout
     types_out = t.empty(n, dtype=t.int16, device=dev)
     state = t.empty(n, dtype=t.uint8, device=dev)
     cbf = None if conn_first is None else t.empty(nconn + 1, dtype=t.int64, device=dev)
-    total = t.zeros(1, dtype=t.int64, device=dev)
+    total = t.empty(1, dtype=t.int64, device=dev)  # (the call always writes it)
 
     def ptr(x):
         return None if x is None or x.numel() == 0 else x.data_ptr()
@@ -1066,9 +1082,7 @@ def frames_request(method, rid, params, params_offsets, params_lens, table: Rout
         run(out, False)
         return FrameRequest(out, body_offsets, body_lens, types_out, state, cbf, total)
     run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
-    if stream is not None:
-        stream.synchronize()
-    nb = int(total.cpu()[0])
+    nb = _read_back(total, stream)
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FrameRequest(out, body_offsets, body_lens, types_out, state, cbf, nb)
@@ -1083,11 +1097,12 @@ class FrameScan(NamedTuple):
     state: object          # uint8 [nconn]: CONN_OPEN / CONN_CLOSED
     verdict: object        # uint8 [max_frames] (verify=True), else None
     crc: object            # int32 [max_frames] (verify=True), else None
-    nframes: int           # frames found
+    nframes: object        # frames found (int64 [1] on the device with read_count=False)
 
 
 def frames_scan(stream_buf, conn_offsets, conn_lengths, role: str = "server", lift_cap: bool = False,
-                max_frames: Optional[int] = None, verify: bool = False, stream=None, stream_bytes=None):
+                max_frames: Optional[int] = None, verify: bool = False, stream=None, stream_bytes=None,
+                read_count: bool = True):
     """Find the wire frames in raw connection bytes (rpc_frames_scan_device).
 
     Connection c is ``stream_buf[conn_offsets[c] : + conn_lengths[c]]`` (int64/uint64 device
@@ -1095,7 +1110,10 @@ def frames_scan(stream_buf, conn_offsets, conn_lengths, role: str = "server", li
     reference's stop rules (include/rpccrc.h); a trailing partial frame is left for the
     next read: ``consumed[c]`` bytes may be dropped, the rest is the carry-over.
     ``max_frames=None`` counts first, synchronises once and allocates exactly; otherwise
-    the call raises if more than ``max_frames`` frames are found.  ``verify=True`` also
+    the call raises if more than ``max_frames`` frames are found.  With ``max_frames`` and
+    ``read_count=False`` nothing is read back and nothing synchronises: ``nframes`` is a
+    one-element int64 device tensor, and of more than ``max_frames`` frames the first
+    ``max_frames`` are kept (the count still says how many there were).  ``verify=True`` also
     runs frames_verify on the frames found and marks what lies behind a closing frame
     FRAME_NOT_REACHED (rpc_frames_scan_verify_device)."""
     t = _torch()
@@ -1124,10 +1142,10 @@ def frames_scan(stream_buf, conn_offsets, conn_lengths, role: str = "server", li
                   "rpc_frames_scan_verify_device")
 
     def count():  # (the count is read on the call's stream: one synchronisation)
-        if stream is not None:
-            stream.synchronize()
-        return int(nframes.cpu()[0])
+        return _read_back(nframes, stream)
 
+    if max_frames is None and not read_count:
+        raise ValueError("read_count=False needs max_frames")
     if max_frames is None:
         run(0, None, None, None, None)
         cap = count()
@@ -1138,6 +1156,8 @@ def frames_scan(stream_buf, conn_offsets, conn_lengths, role: str = "server", li
     verdict = t.empty(cap, dtype=t.uint8, device=dev) if verify else None
     crc = t.empty(cap, dtype=t.int32, device=dev) if verify else None
     run(cap, offs, conn, verdict, crc)
+    if not read_count:
+        return FrameScan(offs, conn, conn_first, consumed, state, verdict, crc, nframes)
     found = count() if max_frames is not None else cap
     if found > cap:
         raise ValueError(f"frames_scan found {found} frames, max_frames is {cap}")

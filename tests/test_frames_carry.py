@@ -154,12 +154,22 @@ def one_shot(conns, role, lift_cap=False, seed=5):
     return entries_by_conn(u, r.conn_first), host(r.state, np.uint8)
 
 
-def run_rounds(deliveries, role, lift_cap=False, room=rpc_amd.CARRY_ROOM):
+def run_rounds(deliveries, role, lift_cap=False, room=rpc_amd.CARRY_ROOM, stream=None, copy_stream=None):
     """The multi-round loop with the streams on the device, double-buffered: per round the new
     bytes alone go up, to their carry_slots positions; then carry, scan + verify, unpack.  A
     connection that was closed in any round stays closed (the host's sticky flag).  Every
     round's carry is checked against the plain rules on the device's own inputs.  Returns the
-    entries per connection over all rounds, the final flags and each round's plain result."""
+    entries per connection over all rounds, the final flags and each round's plain result.
+    With ``stream`` and ``copy_stream`` (two side streams) each round's H2D goes to the next
+    buffer on ``copy_stream`` from pinned memory, ``stream`` waits on an event recorded behind
+    that copy, and carry, scan + verify and unpack run on ``stream``; the host waits for
+    ``stream`` before it looks at a result."""
+    assert (stream is None) == (copy_stream is None)
+
+    def settle():
+        if stream is not None:
+            stream.synchronize()
+
     nconn = len(deliveries)
     cur = torch.empty(0, dtype=torch.uint8, device=DEV)
     off = ln = used = i64([0] * nconn)
@@ -175,17 +185,29 @@ def run_rounds(deliveries, role, lift_cap=False, room=rpc_amd.CARRY_ROOM):
                        list(zip(host(off, np.uint64), host(ln, np.uint64), host(used, np.uint64), host(sticky, np.uint8))),
                        total, at.tolist(), nl, room)
         want = cc.want_of(case)
-        nxt = to_dev(stage)  # the round's one H2D: new bytes (and headroom) only
-        k = rpc_amd.frames_carry(cur, off, ln, used, sticky, nxt, i64(at), room=room, new_lengths=i64(nl))
+        if stream is None:
+            nxt = to_dev(stage)  # the round's one H2D: new bytes (and headroom) only
+        else:
+            pinned = torch.from_numpy(stage).pin_memory()
+            nxt = torch.empty(total, dtype=torch.uint8, device=DEV)
+            with torch.cuda.stream(copy_stream):
+                nxt.copy_(pinned, non_blocking=True)
+            up = torch.cuda.Event()
+            up.record(copy_stream)
+            stream.wait_event(up)  # (the copy fills the headroom too: the carry writes behind it)
+        k = rpc_amd.frames_carry(cur, off, ln, used, sticky, nxt, i64(at), room=room, new_lengths=i64(nl), stream=stream)
+        settle()
         plain = np.frombuffer(want.next, dtype=np.uint8).copy()
         for c in range(nconn):
             plain[at[c]:at[c] + nl[c]] = stage[at[c]:at[c] + nl[c]]  # (the plain rules know nothing of the new bytes)
         assert nxt.cpu().numpy().tobytes() == plain.tobytes(), rnd
         assert host(k.next_offsets, np.uint64) == want.next_off and host(k.next_lengths, np.uint64) == want.next_len, rnd
         assert host(k.status, np.uint8) == want.status and host(k.carried, np.uint64) == [want.carried], rnd
-        s = rpc_amd.frames_scan(nxt, k.next_offsets, k.next_lengths, role=role, lift_cap=lift_cap, verify=True)
+        s = rpc_amd.frames_scan(nxt, k.next_offsets, k.next_lengths, role=role, lift_cap=lift_cap, verify=True,
+                                stream=stream)
         u = rpc_amd.frames_unpack(nxt, s.frame_offsets, s.verdict, role=role, lift_cap=lift_cap, nul=False,
-                                  conn_first=s.conn_first)
+                                  conn_first=s.conn_first, stream=stream)
+        settle()
         for c, e in enumerate(entries_by_conn(u, s.conn_first)):
             got[c] += e
         sticky = torch.maximum(sticky, s.state)
@@ -212,12 +234,16 @@ def cut_six(conn, role, pattern, after=0):
     return [conn[bounds[i]:bounds[i + 1]] for i in range(6)]
 
 
-@pytest.mark.parametrize("role", ["server", "client"])
-def test_rounds_equal_one_shot(role):
+@pytest.mark.parametrize("role,side_streams", [pytest.param("server", False, id="server"),
+                                               pytest.param("client", False, id="client"),
+                                               pytest.param("server", True, id="server-side_streams"),
+                                               pytest.param("client", True, id="client-side_streams")])
+def test_rounds_equal_one_shot(role, side_streams):
     """48 connections of about 6 KiB with all four endings, each cut into 6 deliveries: the
     entries delivered over the rounds, in order, and the final open / closed state are those of
     one scan + verify + unpack over the whole streams; nothing is delivered after a close; and
-    in some round at least half of the connections carry a non-empty tail."""
+    in some round at least half of the connections carry a non-empty tail.  With side streams
+    the rounds run on a stream of their own and each round's upload on a second one."""
     rng = np.random.default_rng(0xCA221 + (role == "client"))
     conns = [sc.random_conn(rng, 6000, role, ending=sc.ENDINGS[i % 4]) for i in range(48)]
     after = [0] * 48
@@ -231,7 +257,10 @@ def test_rounds_equal_one_shot(role):
         assert b"".join(d) == c
     assert {len(x) for d in deliveries for x in d} >= {0, 1}
     want_entries, want_state = one_shot(conns, role)
-    got, state, wants = run_rounds(deliveries, role)
+    streams = {}
+    if side_streams:
+        streams = {"stream": torch.cuda.Stream(device=DEV), "copy_stream": torch.cuda.Stream(device=DEV)}
+    got, state, wants = run_rounds(deliveries, role, **streams)
     assert state == want_state and {sc.OPEN, sc.CLOSED} == set(state)
     for c in range(48):
         assert got[c] == want_entries[c], c
