@@ -926,6 +926,144 @@ RPCCRC_API int rpc_frames_args_device(const uint8_t *d_bodies, uint64_t bodies_b
                            const uint8_t *d_param_names, uint32_t name_bytes, uint32_t width,
                            uint64_t *d_slots, uint8_t *d_status, int32_t *d_reply_status, void *stream);
 
+/* ---- frame values: typed results and params as JSON text ---------------------
+ * The args' mirror: what sits between the handlers' typed columns and
+ * rpc_frames_reply_device, and between a client's columns and
+ * rpc_frames_request_device.  The reference formats one value at a time, by a
+ * fixed schema: the server's results are one of five types per method
+ * (rpc_server_skeleton.c:162-257), the client's params a fixed list of (name,
+ * type) per method (client/gen/rpc_client_gen.c, the cJSON_Add*ToObject
+ * lines).  This call formats a whole batch from the slots the args leave, so
+ * that only column bytes cross to the host and back.
+ * Entry i has a mode d_mode[i] (NULL: RPC_VALUES_MODE_ENCODE for all), the
+ * handler's verdict d_status[i] (NULL: 0 for all; it may be the args'
+ * d_reply_status with the host's overwrites), a method d_method[i] and `width`
+ * slots d_slots[k * n + i], column-major exactly as the args leave them.
+ * form RPC_VALUES_FORM_RESULT takes one type per method, d_result_types[m]
+ * (RPC_ARG_*), and uses slot 0 only; the four parameter arrays are not looked
+ * at.  form RPC_VALUES_FORM_PARAMS takes the args' four schema arrays
+ * unchanged; d_result_types is not looked at.  For entry i, in this order:
+ *   1. d_status[i] != 0: RPC_VALUES_NONE, size 0 (the reply does not look at
+ *      the value of such an entry).  Nothing else of the entry is looked at.
+ *   2. mode RPC_VALUES_MODE_TEXT: the entry is the host's text
+ *      d_texts[d_text_offsets[i], + d_text_lens[i]), copied verbatim (the
+ *      reply's RAW form, the request's verbatim entries, a DEFER entry the host
+ *      formatted, anything it chose to format itself): RPC_VALUES_TEXT.
+ *      RPC_VALUES_RANGE, with nothing read, if the span does not lie inside
+ *      [0, texts_bytes) or d_text_offsets or d_text_lens is NULL.
+ *   3. Any mode but RPC_VALUES_MODE_ENCODE: RPC_VALUES_NONE, size 0.
+ *   4. RPC_VALUES_BAD_SCHEMA, with no string byte read, if d_method[i] >=
+ *      nmethods; RESULT: if the method's type is not an RPC_ARG_*; PARAMS: if
+ *      the method's two CSR words are not monotone or leave nparams, if it has
+ *      more than `width` parameters, if one of its parameters has an unknown
+ *      type or name words that are not monotone or leave name_bytes (the args'
+ *      rule 2), or a name with a byte the reference would escape (below 0x20,
+ *      '"' or '\').
+ *   5. RPC_VALUES_RANGE, with no string byte read, if a STR slot's span leaves
+ *      the strings: a STR slot is offset | (uint64_t)length << 32, the args'
+ *      encoding, relative to d_str_base[i] (NULL: 0), and d_str_base[i] +
+ *      offset, computed without 64-bit wrap, and the length must lie inside
+ *      [0, strings_bytes).  (With d_strings the unpack's bodies and d_str_base
+ *      its body offsets a handler echoes a string the args found without
+ *      moving it.)
+ *   6. Each value's text, RPC_VALUES_DEFER if one has none here:
+ *      I32   %d of the slot's low 32 bits read as int32_t
+ *            (cJSON_CreateNumber((double)r): every int prints as its digits).
+ *      I64   a JSON string, '"' + %lld + '"': the reference sends i64 quoted in
+ *            both directions (skeleton :183-185, client gen :52-53), and the
+ *            args' I64-from-string path reads it back.
+ *      BOOL  true when the slot is non-zero, else false.
+ *      STR   '"' + the bytes + '"'; bytes >= 0x80 as they are.  A byte below
+ *            0x20, a '"' or a '\' is DEFER: the reference would escape it
+ *            (print_string_ptr), and a 0 byte ends its C string.
+ *      F64   the bytes of print_number (third_party/cJSON.c:591-658) for the
+ *            double d with the slot's bits:
+ *            a. NaN or an infinity: null.
+ *            b. d integer-valued with -2147483648 <= d <= 2147483647: %d.
+ *               -0.0 prints 0; 2147483648.0 is not this case (valueint
+ *               saturates) and prints 2147483648 by d.
+ *            c. d subnormal: DEFER.
+ *            d. t15 = "%.15g" of d, r = strtod(t15); the text is t15 when
+ *               fabs(r - d) <= fmax(fabs(r), fabs(d)) * DBL_EPSILON, evaluated
+ *               in doubles, else "%.17g" of d.  Both correctly rounded, exact
+ *               ties to even, in C's %g shape.  At most 24 bytes.  Not the
+ *               shortest round-trip text: 0.1 + 0.2 prints 0.3 (one ulp away
+ *               keeps 15 digits), 1/3 prints 0.33333333333333331 (17 digits,
+ *               never 16), 9.999999999999999e22 prints 1e+23, 1e-05 but
+ *               0.0001, 1e+15 but 123456789012345, 100000000000000.5 prints
+ *               itself.  Above 1.797693134862315e308 t15 reads back as
+ *               infinity and inf <= inf keeps the 15 digits:
+ *               1.7976931348623157e308 prints 1.79769313486232e+308.
+ *            An F64 value is the rule's bytes or the entry is DEFER, never a
+ *            wrong digit.  The DEFER classes: (1) a subnormal d; (2) a rounding
+ *            the implementation proved it cannot decide: the digits are d's
+ *            significand times a 128-bit power of ten whose error is bounded,
+ *            and a fraction within that bound of one half is undecided unless
+ *            the power is exact (10^0 .. 10^55) or an exact integer compare
+ *            settles it (10^-1 .. 10^-27) -- every tie of a 53-bit significand
+ *            lies in those two ranges, and no double is known to fall in this
+ *            class; (3) a read-back r that leaves the converter's range: r is
+ *            neither normal, nor infinite, nor one of the subnormals beside
+ *            the smallest normal for which step d is decided in integers.
+ *   7. RESULT: the entry is the value text.  PARAMS: '{' + '"name":value' per
+ *      declared parameter in declaration order, joined by ',', + '}', no
+ *      blanks (cJSON_PrintUnformatted); a method without parameters gives {}.
+ *      RPC_VALUES_OK.  An entry over 32 bits is RPC_VALUES_RANGE; that is
+ *      judged from the slots alone, before any string byte is read, a value
+ *      that has no text (rule 6) counting no bytes, nor its name, so it wins
+ *      over DEFER.
+ * Precedence within an entry: BAD_SCHEMA, then RANGE, then DEFER, then OK.
+ * Every entry that is not OK or TEXT has size 0.
+ * d_value_offsets[i] is the exclusive 64-bit sum of the sizes, d_value_lens[i]
+ * the size and *d_total their sum; the layout never depends on out_cap.  An
+ * entry that does not end inside out_cap is not written, not even in part, and
+ * reads RPC_VALUES_NO_ROOM; no byte of d_out outside a written entry is
+ * written; d_out NULL with out_cap 0 is the layout-only call.  *d_ndefer is the
+ * number of DEFER entries: a non-zero count means the host formats those and
+ * calls again with them as TEXT.  d_reply_status[i] is d_status[i] (0 without
+ * one) for NONE, OK and TEXT and -32603 for every other status: an entry
+ * nobody handled answers "Internal error", never a wrong or empty result.
+ * d_out, d_value_offsets, d_value_lens, d_reply_status are the reply's
+ * d_values, d_value_offsets, d_value_lens, d_status in RESULT form and the
+ * request's d_params, d_params_offsets, d_params_lens in PARAMS form.
+ * No byte outside d_strings, d_texts, the slots and the schema arrays is read,
+ * not even by an aligned load window.  All pointers are device pointers; every
+ * output is optional; the call is asynchronous on `stream`.
+ * RPCCRC_EINVAL, before any device is touched: form neither of the two; n *
+ * (PARAMS: width, RESULT: 1) >= 0xFFFFFFFF; width 0 or > RPC_ARGS_MAX_PARAMS;
+ * nmethods > RPC_ROUTE_MAX_METHODS; out_cap > 0 with d_out NULL; n > 0 with
+ * d_method or d_slots NULL; strings_bytes > 0 with d_strings NULL; texts_bytes
+ * > 0 with d_texts NULL; RESULT: nmethods > 0 with d_result_types NULL; PARAMS:
+ * nparams > RPC_ARGS_MAX_SCHEMA_PARAMS, name_bytes > RPC_ARGS_MAX_NAME_BYTES,
+ * nmethods > 0 with d_param_first NULL, nparams > 0 with d_param_types or
+ * d_param_name_off NULL, name_bytes > 0 with d_param_names NULL.  n == 0 with
+ * neither d_total nor d_ndefer is RPCCRC_OK with no device; with them, they
+ * are written as 0. */
+#define RPC_VALUES_NONE 0u       /* nothing to format for this entry */
+#define RPC_VALUES_OK 1u         /* text from the slots */
+#define RPC_VALUES_TEXT 2u       /* the host's text, verbatim */
+#define RPC_VALUES_DEFER 3u      /* a value has no text here: the host formats the entry */
+#define RPC_VALUES_RANGE 4u      /* a span lies outside its buffer, or the entry is over 32 bits: nothing read */
+#define RPC_VALUES_BAD_SCHEMA 5u /* the method's schema words are broken: no string byte read */
+#define RPC_VALUES_NO_ROOM 6u    /* the entry does not end inside out_cap: nothing written */
+#define RPC_VALUES_MODE_NONE 0u
+#define RPC_VALUES_MODE_ENCODE 1u
+#define RPC_VALUES_MODE_TEXT 2u
+#define RPC_VALUES_FORM_RESULT 0
+#define RPC_VALUES_FORM_PARAMS 1
+RPCCRC_API int rpc_frames_values_device(int form, const uint8_t *d_mode, const int32_t *d_status,
+                           const uint16_t *d_method, const uint64_t *d_slots, uint32_t width, uint64_t n,
+                           const uint8_t *d_result_types,
+                           const uint32_t *d_param_first, uint32_t nmethods,
+                           const uint8_t *d_param_types, const uint32_t *d_param_name_off, uint32_t nparams,
+                           const uint8_t *d_param_names, uint32_t name_bytes,
+                           const uint8_t *d_strings, uint64_t strings_bytes, const uint64_t *d_str_base,
+                           const uint8_t *d_texts, uint64_t texts_bytes,
+                           const uint64_t *d_text_offsets, const uint32_t *d_text_lens,
+                           uint8_t *d_out, uint64_t out_cap,
+                           uint64_t *d_value_offsets, uint32_t *d_value_lens, uint8_t *d_values_status,
+                           int32_t *d_reply_status, uint32_t *d_ndefer, uint64_t *d_total, void *stream);
+
 /* ---- batched server receive ring -------------------
  * Replaces the one-frame-at-a-time verify of the reference server loop
  * (server/rpc_server_main.c:135-238, verify at :227) for a receive loop that

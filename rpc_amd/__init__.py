@@ -138,6 +138,21 @@ __all__ = [
     "REQUEST_BAD_METHOD",
     "REQUEST_RANGE",
     "REQUEST_NO_ROOM",
+    "frames_values",
+    "FrameValues",
+    "result_types",
+    "VALUES_NONE",
+    "VALUES_OK",
+    "VALUES_TEXT",
+    "VALUES_DEFER",
+    "VALUES_RANGE",
+    "VALUES_BAD_SCHEMA",
+    "VALUES_NO_ROOM",
+    "VALUES_MODE_NONE",
+    "VALUES_MODE_ENCODE",
+    "VALUES_MODE_TEXT",
+    "VALUES_FORM_RESULT",
+    "VALUES_FORM_PARAMS",
 ]
 
 # reference rpc.h:11-17
@@ -220,6 +235,19 @@ REQUEST_RAW = 2
 REQUEST_BAD_METHOD = 3
 REQUEST_RANGE = 4
 REQUEST_NO_ROOM = 5
+# frames_values (include/rpccrc.h RPC_VALUES_*)
+VALUES_NONE = 0
+VALUES_OK = 1
+VALUES_TEXT = 2
+VALUES_DEFER = 3
+VALUES_RANGE = 4
+VALUES_BAD_SCHEMA = 5
+VALUES_NO_ROOM = 6
+VALUES_MODE_NONE = 0
+VALUES_MODE_ENCODE = 1
+VALUES_MODE_TEXT = 2
+VALUES_FORM_RESULT = 0
+VALUES_FORM_PARAMS = 1
 
 
 def _as_buffer(data) -> tuple[Optional[int], int, object]:
@@ -1086,6 +1114,112 @@ def frames_request(method, rid, params, params_offsets, params_lens, table: Rout
     out = t.empty(nb, dtype=t.uint8, device=dev)
     run(out, False)
     return FrameRequest(out, body_offsets, body_lens, types_out, state, cbf, nb)
+
+
+def result_types(methods, results, device=None):
+    """The ``d_result_types`` tensor of frames_values' RESULT form: ``results[m]`` is the result
+    type of ``methods[m]`` (the list ``args_schema`` and ``route_table`` are built from), an
+    ``ARG_*`` constant or one of the IDL's names."""
+    t = _torch()
+    if len(results) != len(methods):
+        raise ValueError("one result type per method")
+    if len(results) > ROUTE_MAX_METHODS:
+        raise ValueError(f"at most {ROUTE_MAX_METHODS} methods")
+    codes = [_ARG_TYPES[r] if isinstance(r, str) else int(r) for r in results]
+    return t.tensor(codes, dtype=t.uint8).to("cuda" if device is None else device)
+
+
+class FrameValues(NamedTuple):
+    """What frames_values returns (device tensors; ``total`` is the host-side byte count, or with
+    a caller's ``out`` -- nothing is read back then -- a one-element int64 device tensor)."""
+    values: object         # uint8: the value texts back to back
+    value_offsets: object  # int64 [n]: where each entry's text starts
+    value_lens: object     # int32 [n]: its length (view as uint32)
+    status: object         # uint8 [n]: VALUES_NONE / _OK / _TEXT / _DEFER / _RANGE / _BAD_SCHEMA / _NO_ROOM
+    reply_status: object   # int32 [n]: the given status, or -32603 for an entry nobody formatted
+    ndefer: object         # int32 [1]: the number of VALUES_DEFER entries
+    total: object          # bytes of all entries, whether they fitted or not
+
+
+def frames_values(method, slots, schema, form: int = VALUES_FORM_RESULT, mode=None, status=None, strings=None,
+                  str_base=None, texts=None, text_offsets=None, text_lens=None, out=None, stream=None) -> FrameValues:
+    """Typed results or params as JSON text (rpc_frames_values_device): the args' mirror, what
+    sits between the handlers' columns and ``frames_reply`` (RESULT form) and between a client's
+    columns and ``frames_request`` (PARAMS form).
+
+    ``slots`` is an 8-byte tensor ``[width, n]``, column-major as ``frames_args`` leaves it: an
+    I32 / I64 / BOOL slot is the value, an F64 slot the double's bits, a STR slot
+    ``offset | length << 32`` into ``strings``, relative to ``str_base[i]``.  ``schema`` is
+    ``result_types(...)`` in RESULT form (slot 0 is the result) and ``args_schema(...)`` in PARAMS
+    form.  ``mode[i]`` (``None``: ENCODE) picks VALUES_MODE_NONE, _ENCODE or _TEXT, the host's own
+    text ``texts[text_offsets[i] : + text_lens[i]]``; an entry with ``status[i] != 0`` has no
+    value.  A double's text is cJSON's print_number byte for byte; strings that need an escape
+    and subnormals read VALUES_DEFER: format those on the host and call again with them as TEXT
+    (``ndefer`` says whether there are any).  ``values, value_offsets, value_lens, reply_status``
+    go to ``frames_reply`` as ``values, value_offsets, value_lens, status``, or the first three to
+    ``frames_request`` as its params.
+
+    ``out=None`` makes the layout-only call first, reads the total (one synchronisation),
+    allocates exactly and builds.  With ``out`` nothing is read back: entries that do not end
+    inside it are VALUES_NO_ROOM and not written, and ``total`` stays on the device."""
+    t = _torch()
+    n = method.numel()
+    params = form == VALUES_FORM_PARAMS
+    if slots.dim() != 2 or slots.element_size() != 8 or not slots.is_contiguous() or slots.shape[1] != n:
+        raise ValueError(f"slots must be a contiguous 8-byte tensor [width, {n}]")
+    width = slots.shape[0]
+    for name, x, size in (("method", method, 2), ("mode", mode, 1), ("status", status, 4), ("str_base", str_base, 8),
+                          ("text_offsets", text_offsets, 8), ("text_lens", text_lens, 4)):
+        if x is None:
+            continue
+        if x.numel() != n or x.element_size() != size or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {size}-byte tensor with n = {n} elements")
+    for name, x in (("strings", strings), ("texts", texts), ("out", out)):
+        if x is not None and (x.element_size() != 1 or not x.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous uint8 tensor")
+    if params:
+        if (schema.first.numel() != schema.nmethods + 1 or schema.types.numel() != schema.nparams or
+                schema.name_off.numel() != schema.nparams + 1 or schema.first.element_size() != 4 or
+                schema.types.element_size() != 1 or schema.name_off.element_size() != 4):
+            raise ValueError("schema needs nmethods + 1 4-byte CSR words, nparams types and nparams + 1 4-byte name words")
+    elif schema.element_size() != 1 or not schema.is_contiguous():
+        raise ValueError("result types must be a contiguous uint8 tensor")
+    dev = method.device
+    sh = _stream_handle(stream)
+    value_offsets = t.empty(n, dtype=t.int64, device=dev)
+    value_lens = t.empty(n, dtype=t.int32, device=dev)
+    state = t.empty(n, dtype=t.uint8, device=dev)
+    reply_status = t.empty(n, dtype=t.int32, device=dev)
+    ndefer = t.empty(1, dtype=t.int32, device=dev)
+    total = t.empty(1, dtype=t.int64, device=dev)
+
+    def ptr(x):
+        return None if x is None or x.numel() == 0 else x.data_ptr()
+
+    if params:
+        sch = (None, ptr(schema.first), schema.nmethods, ptr(schema.types), ptr(schema.name_off), schema.nparams,
+               ptr(schema.names), schema.names.numel())
+    else:
+        sch = (ptr(schema), None, schema.numel(), None, None, 0, None, 0)
+
+    def run(dst, layout_only):
+        outs = (None,) * 5 if layout_only else (ptr(value_offsets), ptr(value_lens), ptr(state), ptr(reply_status),
+                                                ndefer.data_ptr())
+        check(_lib.rpc_frames_values_device(int(form), ptr(mode), ptr(status), ptr(method), ptr(slots), width, n, *sch,
+                                            ptr(strings), strings.numel() if ptr(strings) else 0, ptr(str_base),
+                                            ptr(texts), texts.numel() if ptr(texts) else 0, ptr(text_offsets),
+                                            ptr(text_lens), ptr(dst), 0 if dst is None else dst.numel(), *outs,
+                                            total.data_ptr(), sh),
+              "rpc_frames_values_device")
+
+    if out is not None:
+        run(out, False)
+        return FrameValues(out, value_offsets, value_lens, state, reply_status, ndefer, total)
+    run(None, True)  # layout only: the total (read on the call's stream: one synchronisation)
+    nb = _read_back(total, stream)
+    out = t.empty(nb, dtype=t.uint8, device=dev)
+    run(out, False)
+    return FrameValues(out, value_offsets, value_lens, state, reply_status, ndefer, nb)
 
 
 class FrameScan(NamedTuple):

@@ -84,6 +84,9 @@ rpc_frames_reply_device = _sig("rpc_frames_reply_device", _i32, _vp, _vp, _vp, _
                                _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_request_device = _sig("rpc_frames_request_device", _i32, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _u64, _vp,
                                  _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+rpc_frames_values_device = _sig("rpc_frames_values_device", _i32, _i32, _vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _u32, _vp,
+                                _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp)
 rpc_frames_scan_device = _sig("rpc_frames_scan_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp, _u64, _vp, _vp, _vp,
                               _vp, _vp)
 rpc_frames_scan_verify_device = _sig("rpc_frames_scan_verify_device", _i32, _vp, _u64, _vp, _vp, _u64, _i32, _vp, _vp,
@@ -138,6 +141,7 @@ EXPORTS = (
     "rpc_frames_args_device",
     "rpc_frames_reply_device",
     "rpc_frames_request_device",
+    "rpc_frames_values_device",
     "rpc_frames_scan_device",
     "rpc_frames_scan_verify_device",
     "rpc_frames_set_scan_path",

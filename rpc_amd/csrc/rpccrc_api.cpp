@@ -41,6 +41,7 @@
 #include "frames_scan.h"
 #include "frames_reply.h"
 #include "frames_request.h"
+#include "frames_values.h"
 #include "frames_resolve.h"
 #include "frames_route.h"
 #include "frames_unpack.h"
@@ -2276,6 +2277,99 @@ int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const i
   a.conn_bytes_first = d_conn_bytes_first;
   a.total = d_total;
   return map_hip(launch_frames_reply(a, s));
+}
+
+int rpc_frames_values_device(int form, const uint8_t *d_mode, const int32_t *d_status, const uint16_t *d_method,
+                             const uint64_t *d_slots, uint32_t width, uint64_t n, const uint8_t *d_result_types,
+                             const uint32_t *d_param_first, uint32_t nmethods, const uint8_t *d_param_types,
+                             const uint32_t *d_param_name_off, uint32_t nparams, const uint8_t *d_param_names,
+                             uint32_t name_bytes, const uint8_t *d_strings, uint64_t strings_bytes,
+                             const uint64_t *d_str_base, const uint8_t *d_texts, uint64_t texts_bytes,
+                             const uint64_t *d_text_offsets, const uint32_t *d_text_lens, uint8_t *d_out,
+                             uint64_t out_cap, uint64_t *d_value_offsets, uint32_t *d_value_lens,
+                             uint8_t *d_values_status, int32_t *d_reply_status, uint32_t *d_ndefer, uint64_t *d_total,
+                             void *stream) {
+  if (form != RPC_VALUES_FORM_RESULT && form != RPC_VALUES_FORM_PARAMS) return RPCCRC_EINVAL;
+  if (!frames_layout_args_ok(n, d_out, out_cap, nullptr, 0, nullptr)) return RPCCRC_EINVAL;
+  if (width == 0 || width > RPC_ARGS_MAX_PARAMS) return RPCCRC_EINVAL;
+  if (nmethods > RPC_ROUTE_MAX_METHODS) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_method || !d_slots)) return RPCCRC_EINVAL;
+  const bool params = form == RPC_VALUES_FORM_PARAMS;
+  if (params) {
+    if (nparams > RPC_ARGS_MAX_SCHEMA_PARAMS || name_bytes > RPC_ARGS_MAX_NAME_BYTES) return RPCCRC_EINVAL;
+    if (nmethods > 0 && !d_param_first) return RPCCRC_EINVAL;
+    if (nparams > 0 && (!d_param_types || !d_param_name_off)) return RPCCRC_EINVAL;
+    if (name_bytes > 0 && !d_param_names) return RPCCRC_EINVAL;
+  } else if (nmethods > 0 && !d_result_types) {
+    return RPCCRC_EINVAL;
+  }
+  if (strings_bytes > 0 && !d_strings) return RPCCRC_EINVAL;
+  if (texts_bytes > 0 && !d_texts) return RPCCRC_EINVAL;
+  const uint32_t unit = params ? width : 1u;
+  if (n * unit >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (n == 0 && !d_total && !d_ndefer) return RPCCRC_OK;
+  DeviceCtx *c = nullptr;
+  int rc = get_async_ctx(&c);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    if (d_ndefer) RPCCRC_TRY(hipMemsetAsync(d_ndefer, 0, sizeof(uint32_t), s));
+    return frames_layout_empty(d_total, nullptr, 0, s);
+  }
+  const uint64_t items = n * unit;
+  const size_t tmp_words = scan_tmp_words(items);
+  ValuesArgs a;
+  Lease wsl;
+  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
+    a.sizes = w.take<uint64_t>(items);
+    a.src_off = w.take<uint64_t>(items);
+    a.offs = w.take<uint64_t>(items + 1);
+    a.scan_tmp = w.take<uint64_t>(tmp_words);
+    a.text0 = w.take<uint64_t>(items);
+    a.text1 = w.take<uint64_t>(items);
+    a.text2 = w.take<uint64_t>(items);
+    a.long_off = w.take<uint64_t>(items);
+    a.meta = w.take<uint32_t>(items);
+    a.long_len = w.take<uint32_t>(items);
+    a.long_entry = w.take<uint32_t>(items);
+    a.long_bad = w.take<uint32_t>(items);
+    a.long_count = w.take<uint32_t>(1);
+    a.pre = w.take<uint8_t>(n);
+  });
+  if (rc) return rc;
+  a.form = form;
+  a.mode = d_mode;
+  a.status = d_status;
+  a.method = d_method;
+  a.slots = d_slots;
+  a.width = width;
+  a.n = n;
+  a.result_types = d_result_types;
+  a.param_first = d_param_first;
+  a.nmethods = nmethods;
+  a.param_types = d_param_types;
+  a.param_name_off = d_param_name_off;
+  a.nparams = params ? nparams : 0;
+  a.param_names = d_param_names;
+  a.name_bytes = params ? name_bytes : 0;
+  a.strings = d_strings;
+  a.strings_bytes = strings_bytes;
+  a.str_base = d_str_base;
+  a.texts = d_texts;
+  a.texts_bytes = texts_bytes;
+  a.text_off = d_text_offsets;
+  a.text_len = d_text_lens;
+  a.out = d_out;
+  a.out_cap = out_cap;
+  a.value_off = d_value_offsets;
+  a.value_len = d_value_lens;
+  a.values_status = d_values_status;
+  a.reply_status = d_reply_status;
+  a.ndefer = d_ndefer;
+  a.total = d_total;
+  a.unit = unit;
+  a.items = items;
+  return map_hip(launch_frames_values(a, s));
 }
 
 int rpc_frames_request_device(const uint16_t *d_method, const uint32_t *d_id, const uint16_t *d_types, uint64_t n,
