@@ -14,18 +14,20 @@
 //
 // (client/rpc_codec.c:6-20 through cJSON_PrintUnformatted).  The name counts as
 // generated: its bytes come from the method table (the kernel's copy in LDS), so
-// the copied middle stays single and the reply's machinery serves unchanged --
-// tiles aligned to the output's address, whole 16-byte pieces, the value bytes
-// through two aligned blocks and the funnel; request_piece() resolves one piece.
+// the copied middle stays single and the reply's machinery, the splice
+// (frames_splice.h), serves unchanged -- tiles aligned to the output's address,
+// whole 16-byte pieces, the value bytes through two aligned blocks and the
+// funnel; splice_piece() resolves one piece over RequestSplice, the request's
+// policy.
 // A front can be 27 + 4096 + 11 bytes, so the per-entry word is 32 bits wide:
 // form, the suffix's length (it depends on the id's digits) and the front's.
 // The fixed texts are immediates picked by selects and the digits are BCD
-// (reply_bcd and its kin, used from frames_reply.h as they stand).
+// (splice_bcd and its kin).
 //
 // Plain inline code with no HIP types, shared by the kernels
 // (frames_request.hip) and the CPU emulator (tests/cpu_emu/request_emu.cpp).
 #pragma once
-#include "frames_reply.h"
+#include "frames_splice.h"
 
 namespace rpccrc {
 
@@ -52,13 +54,16 @@ constexpr char kReqIdText[] = ",\"id\":";
 constexpr uint32_t kReqHeadN = sizeof(kReqHeadText) - 1, kReqParamsN = sizeof(kReqParamsText) - 1,
                    kReqIdN = sizeof(kReqIdText) - 1;
 static_assert(kReqHeadN == 27 && kReqParamsN == 10 && kReqIdN == 6, "the sizes of include/rpccrc.h: 45 and 35");
-constexpr uint64_t kReqHead0 = reply_lit8(kReqHeadText, kReqHeadN, 0), kReqHead1 = reply_lit8(kReqHeadText, kReqHeadN, 1),
-                   kReqHead2 = reply_lit8(kReqHeadText, kReqHeadN, 2), kReqHead3 = reply_lit8(kReqHeadText, kReqHeadN, 3);
-constexpr uint64_t kReqParams0 = reply_lit8(kReqParamsText, kReqParamsN, 0),
-                   kReqParams1 = reply_lit8(kReqParamsText, kReqParamsN, 1);
-constexpr uint64_t kReqId0 = reply_lit8(kReqIdText, kReqIdN, 0);
+constexpr uint64_t kReqHead0 = splice_lit8(kReqHeadText, kReqHeadN, 0),
+                   kReqHead1 = splice_lit8(kReqHeadText, kReqHeadN, 1),
+                   kReqHead2 = splice_lit8(kReqHeadText, kReqHeadN, 2),
+                   kReqHead3 = splice_lit8(kReqHeadText, kReqHeadN, 3);
+constexpr uint64_t kReqParams0 = splice_lit8(kReqParamsText, kReqParamsN, 0),
+                   kReqParams1 = splice_lit8(kReqParamsText, kReqParamsN, 1);
+constexpr uint64_t kReqId0 = splice_lit8(kReqIdText, kReqIdN, 0);
 PACK_HD uint32_t request_head_byte(uint32_t i) { // i < 27
-  return i < 24 ? reply_text_byte(kReqHead0, kReqHead1, kReqHead2, i) : (uint32_t)(kReqHead3 >> (8 * (i & 7u))) & 0xFFu;
+  return i < 24 ? splice_text_byte(kReqHead0, kReqHead1, kReqHead2, i)
+                : (uint32_t)(kReqHead3 >> (8 * (i & 7u))) & 0xFFu;
 }
 
 // ---- the method table (rule 3) --------------------------------------------------
@@ -123,7 +128,7 @@ PACK_HD RequestSize request_size_one(const In &in, const Names &names, bool type
   const uint32_t len = in.plen();
   if (!(off <= params_bytes && len <= params_bytes - off)) return RequestSize{0, 0, request_meta(kReqFormRange, 0, 0)};
   if (raw) return len ? RequestSize{len, off, request_meta(kReqFormRaw, 0, 0)} : none;
-  const uint32_t idn = reply_ndigits(in.id());
+  const uint32_t idn = splice_ndigits(in.id());
   if (len != 0) {
     const uint32_t pre = kReqHeadN + nlen + 1 + kReqParamsN, suf = kReqIdN + idn + 1;
     const uint64_t size = (uint64_t)pre + len + suf;
@@ -150,11 +155,11 @@ struct RequestGen {
   uint32_t noff, nlen; // the name in the table
   bool value;          // `,"params":` follows the name
   uint32_t idn;        // characters of the id
-  uint64_t idd;        // reply_bcd of it
+  uint64_t idd;        // splice_bcd of it
 };
 template <class Tab> PACK_HD RequestGen request_gen(uint32_t meta, uint32_t method, uint32_t id, const Tab &tab) {
   const uint32_t a = tab.off(method);
-  return RequestGen{a, tab.off(method + 1) - a, request_form(meta) == kReqFormValue, reply_ndigits(id), reply_bcd(id)};
+  return RequestGen{a, tab.off(method + 1) - a, request_form(meta) == kReqFormValue, splice_ndigits(id), splice_bcd(id)};
 }
 // Generated byte g of a call: the bytes in front of the copied ones and the
 // bytes behind them, counted through.
@@ -166,70 +171,43 @@ template <class Tab> PACK_HD uint32_t request_gen_byte(const RequestGen &t, cons
   if (g == 0) return '"';
   g -= 1;
   if (t.value) {
-    if (g < kReqParamsN) return reply_text_byte(kReqParams0, kReqParams1, 0, g);
+    if (g < kReqParamsN) return splice_text_byte(kReqParams0, kReqParams1, 0, g);
     g -= kReqParamsN;
   }
-  if (g < kReqIdN) return reply_text_byte(kReqId0, 0, 0, g);
+  if (g < kReqIdN) return splice_text_byte(kReqId0, 0, 0, g);
   g -= kReqIdN;
-  if (g < t.idn) return reply_digit(t.idd, t.idn, g);
+  if (g < t.idn) return splice_digit(t.idd, t.idn, g);
   return '}';
 }
 
-// ---- the piece resolver ----------------------------------------------------
-// One 16-byte piece (PackPiece: the words and the bytes to store).  A byte is
-// stored iff it belongs to an entry that is written.
-// Ent: the entries.
+// ---- the splice policy -------------------------------------------------------
+// The request under splice_piece() (frames_splice.h).  Ent: the entries.
 //   uint32_t meta(e), method(e), id(e)   (method and id: asked for only when a byte is generated)
-// Tab: the method table, as above; SrcOf, Src, the piece and [lo, hi] as in
-// frames_reply.h (reply_piece_is_middle tells the fast pieces here too).
+// Tab: the method table, as above; Src: the params.  An entry is written when it
+// ends inside out_cap.
+template <class Ent, class Tab, class Src> struct RequestSplice {
+  const Ent &ent;
+  const Tab &tab;
+  const Src &params;
+  uint64_t out_cap;
+  struct Gen {
+    RequestGen t;
+    const Tab &tab;
+    PACK_HD uint32_t byte(uint32_t g) const { return request_gen_byte(t, tab, g); }
+  };
+  PACK_HD bool written(uint64_t, uint64_t fe) const { return fe <= out_cap; }
+  PACK_HD uint32_t meta(uint64_t e) const { return ent.meta(e); }
+  PACK_HD uint32_t pre(uint32_t m) const { return request_pre(m); }
+  PACK_HD uint32_t suf(uint32_t m) const { return request_suf(m); }
+  PACK_HD Gen gen(uint64_t e, uint32_t m) const { return Gen{request_gen(m, ent.method(e), ent.id(e), tab), tab}; }
+  PACK_HD const Src &src(uint32_t) const { return params; }
+};
+// One piece of the request from its readers: splice_piece() over the policy.
+// SrcOf, the piece and [lo, hi] as there.
 template <class Off, class Ent, class Tab, class SrcOf, class Src>
 PACK_HD PackPiece request_piece(const Off &off, const Ent &ent, const Tab &tab, const SrcOf &src_of, const Src &src,
                                 uint64_t lo, uint64_t hi, uint64_t x0, uint64_t x1, uint32_t b0, uint64_t out_cap) {
-  PackPiece p{{0, 0, 0, 0}, 0};
-  uint64_t x = x0;
-  uint32_t b = b0;
-  uint64_t e = pack_find(off, lo, hi, x); // the last entry with offset <= x covers x (see pack_find)
-  for (;;) {
-    const uint64_t fo = off(e), fe = off(e + 1);
-    const uint32_t cnt = (uint32_t)((fe < x1 ? fe : x1) - x); // >= 1: fe > x
-    if (fe <= out_cap) { // the entry is written
-      const uint32_t m = ent.meta(e);
-      const uint32_t pre = request_pre(m), suf = request_suf(m);
-      const uint64_t at = x - fo, end = at + cnt, mid_end = fe - fo - suf; // entry bytes [pre, mid_end) are copied
-      if (at < pre || end > mid_end) {
-        const RequestGen t = request_gen(m, ent.method(e), ent.id(e), tab);
-        const uint32_t mid = (uint32_t)(mid_end - pre);
-        for (uint32_t i = 0; i < cnt; ++i) {
-          const uint64_t pos = at + i;
-          if (pos < pre)
-            reply_put(&p, b + i, request_gen_byte(t, tab, (uint32_t)pos));
-          else if (pos >= mid_end)
-            reply_put(&p, b + i, request_gen_byte(t, tab, (uint32_t)(pos - mid)));
-        }
-      }
-      const uint64_t c0 = at > pre ? at : pre, c1 = end < mid_end ? end : mid_end;
-      if (c0 < c1) {
-        const uint32_t bb = b + (uint32_t)(c0 - at), bc = (uint32_t)(c1 - c0);
-        const uint64_t s = src_of(e) + (c0 - pre);
-        uint32_t win[4];
-        if (pack_window(src, s, bb, win)) {
-          PACK_UNROLL
-          for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t mk = pack_range_mask(j, bb, bb + bc);
-            p.w[j] = (p.w[j] & ~mk) | (win[j] & mk);
-          }
-        } else { // a window that would leave the params: bytewise
-          for (uint32_t i = 0; i < bc; ++i) reply_put(&p, bb + i, src.byte(s + i));
-        }
-      }
-      p.mask |= ((1u << cnt) - 1u) << b;
-    }
-    x += cnt;
-    b += cnt;
-    if (x >= x1) break;
-    e = unpack_next(off, e, hi, x);
-  }
-  return p;
+  return splice_piece(RequestSplice<Ent, Tab, Src>{ent, tab, src, out_cap}, off, src_of, lo, hi, x0, x1, b0);
 }
 
 // ---- workspace -------------------------------------------------------------------

@@ -1,8 +1,11 @@
 // rpc_amd/csrc/frames_tile.h -- the device side of the destination-centric copy
 // that the frame pack, unpack and carry share (frames_pack.hip,
-// frames_unpack.hip, frames_carry.hip; the rules they run: frames_pack.h): the
+// frames_unpack.hip, frames_carry.hip; the rules they run: frames_pack.h) and
+// that the reply, the request and the values run through frames_splice.h: the
 // readers of the layout and of the source, the wave-wide entry search, the
-// masked store, a tile's entry range with its LDS staging, and the lane walker.
+// masked store, a tile's entry range with its LDS staging, the lane walker, and
+// the tile driver that is the body of the unpack, reply, request and values
+// kernels.
 #pragma once
 #include "frames_pack.h"
 
@@ -169,6 +172,43 @@ __device__ __forceinline__ void tile_walk(const uint8_t *src, uint8_t *dst, cons
   // walks its own set bits, so a wave makes as many rounds as its busiest lane
   // has such pieces -- mostly one -- not one round per k.)
   for (; slow; slow &= slow - 1) slow_store((uint32_t)__ffs((int)slow) - 1u);
+}
+
+// An output of `total` laid-out bytes at `out`, cut at out_cap, as tiles.
+struct TileOut {
+  uint64_t total;
+  uint32_t mis;    // out's low four address bits
+  uint8_t *out0;   // out - mis: 16-byte aligned; bytes before out are never touched
+  uint64_t ntiles; // nothing at or beyond out_cap is ever written, so tiles beyond it have no work
+};
+__device__ __forceinline__ TileOut tile_out(const uint64_t *offs, uint64_t n, uint8_t *out, uint64_t out_cap) {
+  const uint64_t total = offs[n];
+  const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
+  return TileOut{total, mis, out - mis, pack_tiles(total < out_cap ? total : out_cap, mis, kPackTile)};
+}
+// The tile driver: one workgroup of kThreads per tile of kPackTile output bytes
+// (striding when the grid is smaller).  Per tile: tile_range over the n entries'
+// layout and source offsets, then
+//   tile(off, src_of, out0, tile index, mis, tile_x1, lo0, hi)
+// with the readers of the staged slices or, when the range did not fit, of
+// global memory; tile_x1: the layout offset the tile's bytes end at; [lo0, hi]:
+// the entries covering its first and last byte.  (Scalars, not a struct: through
+// one the compiler lost that mis < 16 and pack_span() kept a branch per piece.)
+// s_off and s_src hold kTileLdsEntries words.
+template <int kThreads, class Tile>
+__device__ __forceinline__ void tile_drive(const uint64_t *offs, const uint64_t *src_off, uint64_t n, uint8_t *out,
+                                           uint64_t out_cap, uint64_t s_range[2], uint64_t *s_off, uint64_t *s_src,
+                                           const Tile tile) {
+  const TileOut o = tile_out(offs, n, out, out_cap);
+  for (uint64_t t = blockIdx.x; t < o.ntiles; t += gridDim.x) {
+    const PackSpan ts = pack_span(t * kPackTile, kPackTile, o.mis, o.total); // x0 < x1: the tile holds a byte
+    const TileRange r = tile_range<kThreads>(offs, src_off, n, ts.x0, ts.x1 - 1, s_range, s_off, s_src);
+    if (r.staged)
+      tile(LdsOff{s_off, r.lo0}, LdsOff{s_src, r.lo0}, o.out0, t, o.mis, ts.x1, r.lo0, r.hi);
+    else
+      tile(DevOff{offs}, DevOff{src_off}, o.out0, t, o.mis, ts.x1, r.lo0, r.hi);
+    __syncthreads(); // s_range, s_off and s_src are rewritten for the next tile
+  }
 }
 
 } // namespace rpccrc

@@ -1,7 +1,7 @@
 // rpc_amd/csrc/frames_unpack.hip -- device-side frame unpack
 // (rpc_frames_unpack_device; the rules and the piece resolver: frames_unpack.h;
-// the tile range, the lane walker, the search and the store: frames_tile.h;
-// DESIGN.md 4.13).
+// the tile driver, the tile range, the lane walker, the search and the store:
+// frames_tile.h).
 //
 //   size pass -> exclusive scan (the layout) -> unpack kernel -> finish pass
 #include <algorithm>
@@ -84,21 +84,11 @@ __device__ __forceinline__ void unpack_tile(const UnpackArgs &a, const Off off, 
 __global__ __launch_bounds__(kUnpackThreads) __attribute__((amdgpu_waves_per_eu(5))) void unpack_kernel(UnpackArgs a) {
   __shared__ uint64_t s_range[2];
   __shared__ uint64_t s_off[kTileLdsEntries], s_src[kTileLdsEntries];
-  const uint64_t total = a.offs[a.n];
-  const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(a.out) & 15u);
-  uint8_t *const out0 = a.out - mis; // 16-byte aligned; bytes before a.out are never touched
-  // nothing at or beyond out_cap is ever written, so tiles beyond it have no work
-  const uint64_t ntiles = pack_tiles(total < a.out_cap ? total : a.out_cap, mis, kPackTile);
   const DevSrc src{a.stream, a.stream_bytes};
-  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const PackSpan ts = pack_span(tile * kPackTile, kPackTile, mis, total); // x0 < x1: the tile holds a byte
-    const TileRange r = tile_range<kUnpackThreads>(a.offs, a.src_off, a.n, ts.x0, ts.x1 - 1, s_range, s_off, s_src);
-    if (r.staged)
-      unpack_tile(a, LdsOff{s_off, r.lo0}, LdsOff{s_src, r.lo0}, src, out0, tile, mis, ts.x1, r.lo0, r.hi);
-    else
-      unpack_tile(a, DevOff{a.offs}, DevOff{a.src_off}, src, out0, tile, mis, ts.x1, r.lo0, r.hi);
-    __syncthreads(); // s_range, s_off and s_src are rewritten for the next tile
-  }
+  tile_drive<kUnpackThreads>(a.offs, a.src_off, a.n, a.out, a.out_cap, s_range, s_off, s_src,
+                             [&](const auto off, const auto src_of, auto... tile) {
+                               unpack_tile(a, off, src_of, src, tile...);
+                             });
 }
 
 // ---- finish: final verdicts, reply plan, layout, per-connection byte CSR, total --

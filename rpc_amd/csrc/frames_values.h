@@ -14,9 +14,10 @@
 //   TEXT entry:  the host's bytes                      (all copied)
 //
 // The exclusive scan of the item sizes is the layout; the output is produced
-// with the reply's machinery (frames_reply.h, frames_unpack.h, frames_pack.h),
-// the item taking the place of the reply's entry, so that an entry with
-// several strings still has one copied middle per unit.  Numbers are formatted
+// with the reply's machinery, the splice (frames_splice.h: splice_piece() over
+// ValuesSplice, the values' policy), the item taking the place of the reply's
+// entry, so that an entry with several strings still has one copied middle per
+// unit.  Numbers are formatted
 // once, by values_f64() and its kin, into a 24-byte text record that the write
 // pass only reads.
 //
@@ -35,7 +36,7 @@
 // (frames_values.hip) and the CPU emulator (tests/cpu_emu/values_emu.cpp).
 #pragma once
 #include "frames_args.h"
-#include "frames_reply.h"
+#include "frames_splice.h"
 
 namespace rpccrc {
 
@@ -62,7 +63,7 @@ PACK_HD void vt_put(ValText *t, uint32_t c) {
   t->w2 |= k == 2 ? v : 0;
   ++t->len;
 }
-PACK_HD uint32_t vt_byte(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t i) { return reply_text_byte(w0, w1, w2, i); }
+PACK_HD uint32_t vt_byte(uint64_t w0, uint64_t w1, uint64_t w2, uint32_t i) { return splice_text_byte(w0, w1, w2, i); }
 PACK_HD void vt_lit(ValText *t, const char *s, uint32_t n) {
   for (uint32_t i = 0; i < n; ++i) vt_put(t, (uint8_t)s[i]);
 }
@@ -482,60 +483,40 @@ PACK_HD uint32_t values_gen_byte(uint32_t meta, uint64_t w0, uint64_t w1, uint64
   return '}';
 }
 
-// ---- the piece resolver -------------------------------------------------------------
-// One 16-byte piece, as reply_piece().  Ent: the items.
-//   uint32_t meta(u); uint64_t text(u, j), word j of its record; bool written(u), the
-//   item's entry ends inside out_cap
-// SrcOf: the source offset of item u's copied bytes, in the strings or, for a
-// kItemText item, in the texts.
+// ---- the splice policy ---------------------------------------------------------------
+// The values under splice_piece() (frames_splice.h), the items for its entries.
+// Ent: the items.
+//   uint32_t meta(u); uint64_t text(u, j), word j of its record (asked for only
+//   when a byte of a kItemGen item is generated); bool written(u), the item's
+//   entry ends inside out_cap
+// Schema: as values_gen_byte()'s.  The copied bytes of a kItemText item come
+// from the texts, every other item's from the strings.
+template <class Ent, class Schema, class Src> struct ValuesSplice {
+  const Ent &ent;
+  const Schema &sc;
+  const Src &strings, &texts;
+  struct Gen {
+    uint32_t m;
+    uint64_t w0, w1, w2;
+    const Schema &sc;
+    PACK_HD uint32_t byte(uint32_t g) const { return values_gen_byte(m, w0, w1, w2, sc, g); }
+  };
+  PACK_HD bool written(uint64_t u, uint64_t) const { return ent.written(u); }
+  PACK_HD uint32_t meta(uint64_t u) const { return ent.meta(u); }
+  PACK_HD uint32_t pre(uint32_t m) const { return item_pre(m); }
+  PACK_HD uint32_t suf(uint32_t m) const { return item_suf(m); }
+  PACK_HD Gen gen(uint64_t u, uint32_t m) const {
+    const bool gen = item_kind(m) == kItemGen;
+    return Gen{m, gen ? ent.text(u, 0) : 0, gen ? ent.text(u, 1) : 0, gen ? ent.text(u, 2) : 0, sc};
+  }
+  PACK_HD const Src &src(uint32_t m) const { return item_kind(m) == kItemText ? texts : strings; }
+};
+// One piece of the values from their readers: splice_piece() over the policy.
+// SrcOf, the piece and [lo, hi] as there.
 template <class Off, class Ent, class SrcOf, class Schema, class Src>
 PACK_HD PackPiece values_piece(const Off &off, const Ent &ent, const SrcOf &src_of, const Schema &sc, const Src &strings,
                                const Src &texts, uint64_t lo, uint64_t hi, uint64_t x0, uint64_t x1, uint32_t b0) {
-  PackPiece p{{0, 0, 0, 0}, 0};
-  uint64_t x = x0;
-  uint32_t b = b0;
-  uint64_t e = pack_find(off, lo, hi, x);
-  for (;;) {
-    const uint64_t fo = off(e), fe = off(e + 1);
-    const uint32_t cnt = (uint32_t)((fe < x1 ? fe : x1) - x); // >= 1: fe > x
-    if (ent.written(e)) {
-      const uint32_t m = ent.meta(e);
-      const uint32_t pre = item_pre(m), suf = item_suf(m);
-      const uint64_t at = x - fo, end = at + cnt, mid_end = fe - fo - suf; // item bytes [pre, mid_end) are copied
-      if (at < pre || end > mid_end) {
-        const bool gen = item_kind(m) == kItemGen;
-        const uint64_t w0 = gen ? ent.text(e, 0) : 0, w1 = gen ? ent.text(e, 1) : 0, w2 = gen ? ent.text(e, 2) : 0;
-        const uint32_t mid = (uint32_t)(mid_end - pre);
-        for (uint32_t i = 0; i < cnt; ++i) {
-          const uint64_t pos = at + i;
-          if (pos < pre) reply_put(&p, b + i, values_gen_byte(m, w0, w1, w2, sc, (uint32_t)pos));
-          else if (pos >= mid_end) reply_put(&p, b + i, values_gen_byte(m, w0, w1, w2, sc, (uint32_t)(pos - mid)));
-        }
-      }
-      const uint64_t c0 = at > pre ? at : pre, c1 = end < mid_end ? end : mid_end;
-      if (c0 < c1) {
-        const uint32_t bb = b + (uint32_t)(c0 - at), bc = (uint32_t)(c1 - c0);
-        const uint64_t s = src_of(e) + (c0 - pre);
-        const Src &src = item_kind(m) == kItemText ? texts : strings;
-        uint32_t win[4];
-        if (pack_window(src, s, bb, win)) {
-          PACK_UNROLL
-          for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t mk = pack_range_mask(j, bb, bb + bc);
-            p.w[j] = (p.w[j] & ~mk) | (win[j] & mk);
-          }
-        } else { // a window that would leave the source: bytewise
-          for (uint32_t i = 0; i < bc; ++i) reply_put(&p, bb + i, src.byte(s + i));
-        }
-      }
-      p.mask |= ((1u << cnt) - 1u) << b;
-    }
-    x += cnt;
-    b += cnt;
-    if (x >= x1) break;
-    e = unpack_next(off, e, hi, x);
-  }
-  return p;
+  return splice_piece(ValuesSplice<Ent, Schema, Src>{ent, sc, strings, texts}, off, src_of, lo, hi, x0, x1, b0);
 }
 
 #if defined(__HIPCC__)

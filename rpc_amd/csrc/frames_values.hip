@@ -1,15 +1,12 @@
 // rpc_amd/csrc/frames_values.hip -- device-side frame values
 // (rpc_frames_values_device; the rules, the number formatting, the generated
-// bytes and the piece resolver: frames_values.h; the tile range, the lane
-// walker, the search and the store: frames_tile.h).
+// bytes and the splice policy: frames_values.h; the piece resolver, the tile
+// function and the launch sequence's tail: frames_splice.h; the tile driver:
+// frames_tile.h).
 //
 //   size pass (-> the grid's scan of very long strings) -> exclusive scan (the layout)
 //   -> values kernel -> finish pass
-#include <algorithm>
-
 #include "../../include/rpccrc.h"
-#include "excl_scan.h"
-#include "frames_tile.h"
 #include "frames_values.h"
 
 namespace rpccrc {
@@ -25,10 +22,7 @@ static_assert(kValuesModeNone == RPC_VALUES_MODE_NONE && kValuesModeEncode == RP
 
 namespace {
 
-constexpr int kValuesThreads = 256;
-constexpr uint32_t kPiecesPerLane = kPackTile / kPackPiece / kValuesThreads;
-static_assert(kPiecesPerLane * kPackPiece * kValuesThreads == kPackTile, "a tile is whole rounds of the workgroup");
-constexpr unsigned kValuesMaxGrid = 1u << 18; // workgroups; they stride over the tiles
+constexpr int kValuesThreads = 256; // the size pass and the scan of very long strings
 // A string up to this long is scanned by its entry's lane; a longer one by the
 // whole workgroup, sixteen bytes per lane and round.
 constexpr uint32_t kLaneScan = 256;
@@ -200,64 +194,20 @@ struct DevEnt {
   }
 };
 
-template <class Off>
-__device__ __forceinline__ void values_tile(const ValuesArgs &a, const Off off, const Off src_of, const DevEnt &ent,
-                                            const DevSrc &strings, const DevSrc &texts, uint8_t *out0, uint64_t tile,
-                                            uint32_t mis, uint64_t tile_x1, uint64_t lo0, uint64_t hi) {
-  const auto piece_at = [&](uint32_t k) { return tile * kPackTile + tile_piece(k, kValuesThreads); };
-  // the walker's loads are relative to the strings; a text's block offset is moved by the distance
-  const uint64_t text_delta = texts.addr() - strings.addr();
-  const DevSchema sc{a};
-  uint64_t lo = lo0;
-  tile_walk<kPiecesPerLane>(
-      a.strings, out0, piece_at,
-      [&](uint32_t k) {
-        const PackSpan ps = pack_span(piece_at(k), kPackPiece, mis, tile_x1);
-        TilePlan p{ps.x0 < ps.x1, {false, 0, 0}};
-        if (p.some) {
-          const uint64_t e = pack_find(off, lo, hi, ps.x0);
-          const uint64_t fo = off(e), fe = off(e + 1);
-          lo = e; // (the lane's next piece lies further on)
-          if (fe - fo >= kPackPiece) { // (a shorter item has no whole piece: its meta word stays unread)
-            const uint32_t m = ent.meta(e);
-            const uint32_t pre = item_pre(m);
-            if (reply_piece_is_middle(fo, fe, pre, item_suf(m), ps.x0, ps.x1, ps.b0, ~0ull) && ent.written(e)) {
-              const bool from_texts = item_kind(m) == kItemText;
-              p.w = pack_win_plan(from_texts ? texts : strings, src_of(e) + (ps.x0 - fo - pre), 0);
-              if (from_texts) p.w.blk += text_delta;
-            }
-          }
-        }
-        return p;
-      },
-      [&](uint32_t k) {
-        const PackSpan ps = pack_span(piece_at(k), kPackPiece, mis, tile_x1);
-        store_piece(out0 + piece_at(k), values_piece(off, ent, src_of, sc, strings, texts, lo0, hi, ps.x0, ps.x1, ps.b0));
-      });
-}
-
 // One workgroup per tile of kPackTile output bytes (striding when the grid is
 // smaller), as the reply kernel, over the items in place of the entries.
-__global__ __launch_bounds__(kValuesThreads) void values_kernel(ValuesArgs a) {
+__global__ __launch_bounds__(kSpliceThreads) void values_kernel(ValuesArgs a) {
   __shared__ uint64_t s_range[2];
   __shared__ uint64_t s_off[kTileLdsEntries], s_src[kTileLdsEntries];
-  const uint64_t total = a.offs[a.items];
-  const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(a.out) & 15u);
-  uint8_t *const out0 = a.out - mis; // 16-byte aligned; bytes before a.out are never touched
-  // nothing at or beyond out_cap is ever written, so tiles beyond it have no work
-  const uint64_t ntiles = pack_tiles(total < a.out_cap ? total : a.out_cap, mis, kPackTile);
   const DevSrc strings{a.strings, a.strings_bytes}, texts{a.texts, a.texts_bytes};
-  const DevEnt ent{a, total <= a.out_cap};
-  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const PackSpan ts = pack_span(tile * kPackTile, kPackTile, mis, total); // x0 < x1: the tile holds a byte
-    const TileRange r =
-        tile_range<kValuesThreads>(a.offs, a.src_off, a.items, ts.x0, ts.x1 - 1, s_range, s_off, s_src);
-    if (r.staged)
-      values_tile(a, LdsOff{s_off, r.lo0}, LdsOff{s_src, r.lo0}, ent, strings, texts, out0, tile, mis, ts.x1, r.lo0, r.hi);
-    else
-      values_tile(a, DevOff{a.offs}, DevOff{a.src_off}, ent, strings, texts, out0, tile, mis, ts.x1, r.lo0, r.hi);
-    __syncthreads(); // s_range, s_off and s_src are rewritten for the next tile
-  }
+  const DevEnt ent{a, a.offs[a.items] <= a.out_cap};
+  const DevSchema sc{a};
+  const ValuesSplice<DevEnt, DevSchema, DevSrc> pol{ent, sc, strings, texts};
+  // (the walker's loads are relative to the strings)
+  tile_drive<kSpliceThreads>(a.offs, a.src_off, a.items, a.out, a.out_cap, s_range, s_off, s_src,
+                             [&](const auto off, const auto src_of, auto... tile) {
+                               splice_tile(pol, a.strings, off, src_of, tile...);
+                             });
 }
 
 // ---- finish: statuses, the reply's status words, layout, the DEFER count, total ----
@@ -294,15 +244,7 @@ hipError_t launch_frames_values(const ValuesArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(values_fix_kernel, dim3(kFixGrid), dim3(256), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  if ((e = excl_scan(a.sizes, a.offs, a.items, a.scan_tmp, s)) != hipSuccess) return e;
-  if (a.out && a.out_cap && a.n) {
-    const uint64_t tiles = pack_tiles(a.out_cap, 15, kPackTile);
-    hipLaunchKernelGGL(values_kernel, dim3((unsigned)std::min<uint64_t>(tiles, kValuesMaxGrid)), dim3(kValuesThreads), 0,
-                       s, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(values_finish_kernel, grid_of(a.n, 256), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return splice_launch_tail(a, a.items, a.n, values_kernel, values_finish_kernel, s);
 }
 
 } // namespace rpccrc
