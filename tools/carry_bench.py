@@ -17,10 +17,10 @@ line.
   python tools/carry_bench.py [--conns 16384] [--big 16] [--big-mib 32] [--reps 5] [--rounds 3] [--skip-a] [--skip-b]
 """
 import argparse
+import functools
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -29,35 +29,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import rpc_amd  # noqa: E402
 from rpc_amd import _lib  # noqa: E402
+import bench_common  # noqa: E402
+
+rounds_of = functools.partial(bench_common.rounds_of, name="carry_bench")
 
 CONN_BYTES = 65536
 DEV = torch.device("cuda", 0)
-
-
-def timed(fn, reps, stream, warm=0.2):
-    t0 = time.perf_counter()
-    while True:  # warm-up: code objects, workspace pool, clocks
-        fn()
-        torch.cuda.synchronize()
-        if time.perf_counter() - t0 >= warm:
-            break
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(reps):
-        fn()
-    e1.record(stream)
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
-def rounds_of(legs, reps, rounds, tag):
-    us = {k: [] for k in legs}
-    s = torch.cuda.current_stream()
-    for r in range(rounds):
-        for k, fn in legs.items():
-            us[k].append(timed(fn, reps, s))
-            print(f"carry_bench: {tag} round {r} {k}: {us[k][-1]:.1f} us", file=sys.stderr, flush=True)
-    return {k: {"us": [round(x, 1) for x in v], "median_us": round(float(np.median(v)), 1)} for k, v in us.items()}
 
 
 class Carry:

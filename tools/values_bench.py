@@ -23,6 +23,7 @@ total against the lengths, the big strings against their source.  One JSON line.
   python tools/values_bench.py [--entries 1900000] [--big 16] [--big-mib 64] [--reps 5] [--rounds 3] [--skip abcd]
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -36,6 +37,9 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import rpc_amd  # noqa: E402
 from rpc_amd import _lib  # noqa: E402
+import bench_common  # noqa: E402
+
+rounds_of = functools.partial(bench_common.rounds_of, name="values_bench")
 import args_cases as ac  # noqa: E402
 import values_cases as vc  # noqa: E402
 
@@ -43,32 +47,6 @@ DEV = torch.device("cuda", 0)
 HOST_ENTRIES = 65536
 K = 4096  # template entries
 RTYPES = [vc.STR, vc.I64, vc.I32, vc.F64, vc.BOOL, vc.I32, vc.STR]  # what the seven handlers return
-
-
-def timed(fn, reps, stream, warm=0.2):
-    t0 = time.perf_counter()
-    while True:  # warm-up: code objects, workspace pool, clocks
-        fn()
-        torch.cuda.synchronize()
-        if time.perf_counter() - t0 >= warm:
-            break
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(reps):
-        fn()
-    e1.record(stream)
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
-def rounds_of(legs, reps, rounds, tag):
-    us = {k: [] for k in legs}
-    s = torch.cuda.current_stream()
-    for r in range(rounds):
-        for k, fn in legs.items():
-            us[k].append(timed(fn, reps, s))
-            print(f"values_bench: {tag} round {r} {k}: {us[k][-1]:.1f} us", file=sys.stderr, flush=True)
-    return {k: {"us": [round(x, 1) for x in v], "median_us": round(float(np.median(v)), 1)} for k, v in us.items()}
 
 
 def dev(a):
