@@ -20,6 +20,9 @@
 // load that is not aligned or not wholly inside; the staged reader aborts on a
 // byte outside what the round staged; the table's readers on a cell outside the
 // table and an id outside [0, npending).
+// With RPC_EMU_STAGE_TRACE=<file> in the environment the staging rounds are
+// written there as well, one line per round: "workgroup w0 bodies-taken
+// blocks-read-bytewise" (w0 in aligned space; tests/stage_cases.py, trace()).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -164,6 +167,7 @@ int main(int argc, char **argv) {
   };
   const uint64_t nwg = (n + kRouteEntries - 1) / kRouteEntries;
   std::vector<uint8_t> lds(stage);
+  FILE *trace = getenv("RPC_EMU_STAGE_TRACE") ? fopen(getenv("RPC_EMU_STAGE_TRACE"), "w") : nullptr;
   for (uint64_t w = 0; w < nwg; ++w) {
     const uint64_t wg = visit(w, nwg);
     bool pending[kRouteEntries] = {};
@@ -194,14 +198,19 @@ int main(int argc, char **argv) {
       const uint32_t blocks = (end + 15u) / 16u;
       const uint64_t lim = bodies_bytes + mis;
       std::fill(lds.begin(), lds.end(), (uint8_t)0xA5);
+      uint32_t edge = 0; // blocks read bytewise
       for (uint32_t k = 0; k < blocks; ++k) {
         const uint64_t x = w0 + (uint64_t)k * 16u;
         if (x >= mis && x + 16u <= lim) {
           src.block16(x - mis, lds.data() + 16 * k);
         } else {
+          ++edge;
           for (uint32_t b = 0; b < 16; ++b) lds[16 * k + b] = (x + b >= mis && x + b < lim) ? src.byte(x + b - mis) : 0;
         }
       }
+      if (trace)
+        fprintf(trace, "%llu %llu %u %u\n", (unsigned long long)wg, (unsigned long long)w0,
+                (uint32_t)std::count(mine, mine + kRouteEntries, true), edge);
       for (uint32_t k = 0; k < kRouteEntries; ++k) {
         const uint32_t t = (uint32_t)visit(k, kRouteEntries);
         if (!mine[t]) continue;
@@ -240,5 +249,6 @@ int main(int argc, char **argv) {
     printf(" %lld", (long long)s);
   }
   printf("\n");
+  if (trace) fclose(trace);
   return 0;
 }

@@ -13,6 +13,7 @@ import pytest
 
 import args_cases as ac
 import route_cases as rc
+import stage_cases as sc
 from test_route_emu import S_K, S_SMALL, SHAPES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,3 +110,61 @@ def test_mutations_match_plain_rules(args_emu, stage, mis):
     assert all(w[0] == ac.OK for w in want[:len(canon)])
     n = {s: sum(1 for w in want[len(canon):] if w[0] == s) for s in (ac.OK, ac.INVALID, ac.DEFER)}
     assert sum(n.values()) == len(muts) and min(n.values()) >= 1000, n
+
+
+@pytest.mark.parametrize("stage,odd", [(S_K, 5), (S_SMALL, 11)])
+def test_placements_match_plain_rules(args_emu, stage, odd, monkeypatch):
+    """`params` spans anywhere (tests/stage_cases.py): memory order reversed and shuffled, fixed
+    slots, all lanes on one span and on two far apart, every prefix and suffix of one text, spans
+    that end on a window's last byte and one byte behind it, spans on the buffer's first and last
+    byte at every address, and all of them in one call; each as a body of its own and inside a
+    body that starts up to 40 bytes earlier, with entries of other kinds and garbage offsets on
+    some lanes.  Each input has the property it was built for (by stage_cases.rounds, at the
+    kernel's staging size); status, reply status and slots are the plain rules', and the
+    emulator's rounds are the ones stage_cases.rounds gives at the stage in use, with no block read
+    bytewise that lies wholly inside the buffer."""
+    trace = str(args_emu[1] / "rounds.txt")
+    monkeypatch.setenv("RPC_EMU_STAGE_TRACE", trace)
+
+    def check_placed(emu, stage, mis, buf, entries, schema=ac.IDL, width=ac.MAX_PARAMS, what=""):
+        want = check(emu, stage, mis, buf, entries, schema, width, what)
+        spans = [(e[0] + e[4], e[5]) for e in entries]
+        assert sc.read_trace(trace) == sc.trace(spans, sc.args_walked(buf, entries, schema), mis, len(buf), stage), what
+        return want
+
+    n_of = lambda want: [w[2][0] for w in want]  # noqa: E731
+    for mis in (0, odd):
+        for name in sc.BATCH:
+            p, methods = sc.args_batch(name)
+            strangers = sc.STRANGERS if len(p.spans) == len(sc.args_set()) else ()
+            for lead in (False, True):
+                entries = sc.args_entries(p.spans, methods, lead, strangers)
+                p.holds(sc.args_walked(p.buf, entries), mis)
+                want = check_placed(args_emu, stage, mis, p.buf, entries, what=(name, mis, lead))
+                assert all(want[t][0] == ac.NONE for t in strangers)
+                if name == "nested":
+                    assert sorted(set(n_of(want))) == [0, 2000000031] and sum(w[0] == ac.DEFER for w in want) == len(want) - 2
+        for p in sc.window_edges(sc.params, mis, stage):
+            for lead in (False, True):
+                entries = sc.args_entries(p.spans, [ac.N] * 3, lead)
+                p.holds(sc.args_walked(p.buf, entries), mis)
+                want = check_placed(args_emu, stage, mis, p.buf, entries, what=(p.name, mis, lead))
+                assert n_of(want) == [2000000001, 2000000002, 2000000002]
+        buf, spans, methods = sc.args_mixture(mis)
+        entries = sc.args_entries(spans, methods, True, sc.STRANGERS)
+        check_placed(args_emu, stage, mis, buf, entries, what=("mixture", mis))
+        counts = [len(g) for g in sc.rounds(spans, sc.args_walked(buf, entries), mis)]
+        assert counts[0] >= 128 and counts[1] == 1 and len(counts) >= 4
+    for mis in range(16):
+        p = sc.buffer_ends(sc.params, mis)
+        for lead in (False, True):
+            entries = sc.args_entries(p.spans, [ac.N] * 2, lead)
+            p.holds(sc.args_walked(p.buf, entries), mis)
+            want = check_placed(args_emu, stage, mis, p.buf, entries, what=(p.name, lead))
+            assert n_of(want) == [2000000003, 2000000004]
+        if mis in sc.WHOLE_MIS:
+            p = sc.whole_buffer(sc.WHOLE, mis)
+            entries = sc.args_entries(p.spans, [0])
+            p.holds(sc.args_walked(p.buf, entries, sc.ID_SCHEMA), mis)
+            want = check_placed(args_emu, stage, mis, p.buf, entries, sc.ID_SCHEMA, 1, p.name)
+            assert want == [(ac.OK, 0, (7,))]

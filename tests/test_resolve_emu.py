@@ -14,6 +14,7 @@ import subprocess
 import pytest
 
 import resolve_cases as rc
+import stage_cases as sc
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROUTE_H = os.path.join(REPO, "rpc_amd", "csrc", "frames_route.h")
@@ -149,3 +150,59 @@ def test_mutations_match_plain_rules(resolve_emu, stage, mis):
     assert set(want.kind[len(canon):]) == {rc.MATCHED, rc.UNKNOWN, rc.DUPLICATE, rc.INVALID, rc.DEFER}
     decoded = sum(1 for k in want.kind[len(canon):] if k not in (rc.DEFER, rc.INVALID))
     assert 1000 < decoded < 19000  # both sides of the strict subset are exercised
+
+
+def placed_call(p, pending):
+    return rc.Call(p.buf, [s[0] for s in p.spans], [s[1] for s in p.spans], None, pending)
+
+
+@pytest.mark.parametrize("stage,odd", [(S_K, 5), (S_SMALL, 11)])
+def test_placements_match_plain_rules(resolve_emu, stage, odd, monkeypatch):
+    """Bodies anywhere (tests/stage_cases.py): memory order reversed and shuffled, fixed slots, all
+    lanes on one span and on two far apart, every prefix and suffix of one text, bodies that end
+    on a window's last byte and one byte behind it, bodies on the buffer's first and last byte at
+    every address, and all of them in one call.  Each input has the property it was built for
+    (by stage_cases.rounds, at the kernel's staging size); the whole Resolved tuple, the join
+    included, is the plain rules', and the emulator's rounds are the ones stage_cases.rounds gives
+    at the stage in use, with no block read bytewise that lies wholly inside the buffer."""
+    bodies, pending = sc.resolve_set()
+    trace = str(resolve_emu[1] / "rounds.txt")
+    monkeypatch.setenv("RPC_EMU_STAGE_TRACE", trace)
+
+    def check_placed(emu, stage, mis, call, what):
+        want = check(emu, stage, mis, call, what)
+        spans = list(zip(call.offs, call.lens))
+        assert sc.read_trace(trace) == sc.trace(spans, sc.walked(call.buf, spans), mis, len(call.buf), stage), what
+        return want
+
+    edge_ids = [4000000001 + k for k in (3, 1, 30, 2, 21, 10, 0, 12)]  # (not 11 and 20: nobody waits for them)
+    for mis in (0, odd):
+        for name in sc.BATCH:
+            p = sc.batch(name, bodies, sc.reply)
+            p.holds(sc.walked(p.buf, p.spans), mis)
+            want = check_placed(resolve_emu, stage, mis, placed_call(p, pending + edge_ids), (name, mis))
+            if name == "one body":  # the first lane of a workgroup takes the slot, the others find it taken
+                taken = [rc.MATCHED] + [rc.DUPLICATE] * 255
+                assert want.kind == taken + [rc.UNKNOWN] * 256 + taken
+            if name == "two bodies":
+                assert want.kind == [rc.UNKNOWN, rc.MATCHED] + [rc.UNKNOWN, rc.DUPLICATE] * 127
+            if name == "nested":
+                assert sorted(set(want.id)) == [0, 4000000031] and want.kind.count(rc.DEFER) == len(p.spans) - 2
+        for p in sc.window_edges(sc.reply, mis, stage):
+            p.holds(sc.walked(p.buf, p.spans), mis)
+            want = check_placed(resolve_emu, stage, mis, placed_call(p, edge_ids), (p.name, mis))
+            assert want.id == [4000000001, 4000000002, 4000000002]
+            assert want.kind == [rc.MATCHED, rc.MATCHED, rc.DUPLICATE]
+        buf, spans, placed = sc.mixture(bodies, sc.reply, mis)
+        call = rc.Call(buf, [s[0] for s in spans], [s[1] for s in spans], None, pending + edge_ids)
+        want = check_placed(resolve_emu, stage, mis, call, ("mixture", mis))
+        assert list(zip(want.id, want.result_off, want.result_len, want.error_off, want.error_len)) == \
+            [rc.decode_body(b)[1:] for b in placed]
+        counts = [len(g) for g in sc.rounds(spans, sc.walked(buf, spans), mis)]
+        assert counts[0] >= 128 and counts[1] == 1 and len(counts) >= 4
+    for mis in range(16):
+        ends = [sc.buffer_ends(sc.reply, mis)] + [sc.whole_buffer(sc.WHOLE, mis)] * (mis in sc.WHOLE_MIS)
+        for p in ends:
+            p.holds(sc.walked(p.buf, p.spans), mis)
+            want = check_placed(resolve_emu, stage, mis, placed_call(p, edge_ids + [7]), p.name)
+            assert want.id in ([4000000003, 4000000004], [7]) and set(want.kind) == {rc.MATCHED}

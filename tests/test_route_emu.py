@@ -13,6 +13,7 @@ import subprocess
 import pytest
 
 import route_cases as rc
+import stage_cases as sc
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROUTE_H = os.path.join(REPO, "rpc_amd", "csrc", "frames_route.h")
@@ -137,3 +138,45 @@ def test_mutations_match_plain_rules(route_emu, stage, mis):
     assert {w[0] for w in want[len(canon):]} == {rc.CALL, rc.NOT_FOUND, rc.INVALID, rc.DEFER}
     routed = sum(1 for w in want[len(canon):] if w[0] != rc.DEFER)
     assert 1000 < routed < 19000  # both sides of the strict subset are exercised
+
+
+@pytest.mark.parametrize("stage,odd", [(S_K, 5), (S_SMALL, 11)])
+def test_placements_match_plain_rules(route_emu, stage, odd, monkeypatch):
+    """Bodies anywhere (tests/stage_cases.py): memory order reversed and shuffled, fixed slots, all
+    lanes on one span and on two far apart, every prefix and suffix of one text, bodies that end
+    on a window's last byte and one byte behind it, bodies on the buffer's first and last byte at
+    every address, and all of them in one call.  Each input has the property it was built for
+    (by stage_cases.rounds, at the kernel's staging size); rows and groups are the plain rules',
+    and the emulator's rounds are the ones stage_cases.rounds gives at the stage in use, with no
+    block read bytewise that lies wholly inside the buffer."""
+    bodies = sc.route_set()
+    trace = str(route_emu[1] / "rounds.txt")
+    monkeypatch.setenv("RPC_EMU_STAGE_TRACE", trace)
+
+    def check_placed(emu, stage, mis, buf, spans, types, table, what):
+        want = check(emu, stage, mis, buf, spans, types, table, what)
+        assert sc.read_trace(trace) == sc.trace(spans, sc.walked(buf, spans), mis, len(buf), stage), what
+        return want
+
+    for mis in (0, odd):
+        for name in sc.BATCH:
+            p = sc.batch(name, bodies, sc.request)
+            p.holds(sc.walked(p.buf, p.spans), mis)
+            want = check_placed(route_emu, stage, mis, p.buf, p.spans, None, rc.IDL, (name, mis))
+            if name == "nested":
+                assert {w[2] for w in want} == {0, 4000000031} and len({w for w in want}) == 2
+        for p in sc.window_edges(sc.request, mis, stage):
+            p.holds(sc.walked(p.buf, p.spans), mis)
+            want = check_placed(route_emu, stage, mis, p.buf, p.spans, None, rc.IDL, (p.name, mis))
+            assert [w[2] for w in want] == [4000000001, 4000000002, 4000000002]
+        buf, spans, placed = sc.mixture(bodies, sc.request, mis)
+        want = check_placed(route_emu, stage, mis, buf, spans, None, rc.IDL, ("mixture", mis))
+        assert want == [rc.route_body(b) for b in placed]
+        counts = [len(g) for g in sc.rounds(spans, sc.walked(buf, spans), mis)]
+        assert counts[0] >= 128 and counts[1] == 1 and len(counts) >= 4
+    for mis in range(16):
+        ends = [sc.buffer_ends(sc.request, mis)] + [sc.whole_buffer(sc.WHOLE, mis)] * (mis in sc.WHOLE_MIS)
+        for p in ends:
+            p.holds(sc.walked(p.buf, p.spans), mis)
+            want = check_placed(route_emu, stage, mis, p.buf, p.spans, None, rc.IDL, p.name)
+            assert [w[2] for w in want] in ([4000000003, 4000000004], [7])
