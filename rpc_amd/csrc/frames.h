@@ -2,8 +2,11 @@
 // Frame = 12-byte packed big-endian rpc_header_t (reference rpc.h:3-8,15)
 // followed by body_len bytes.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 
 #include "../../include/rpccrc.h"
 
@@ -12,6 +15,52 @@ namespace rpccrc {
 constexpr uint32_t kFrameHeaderLen = 12; // RPC_HEADER_LEN, rpc.h:15
 constexpr uint8_t kFramePending = 0xFF;  // data frame whose body CRC decides
 
+// The header parse of a verify call: frame i's body offset / effective length,
+// header crc32 and verdict so far.
+struct FramesParse {
+  const uint8_t *stream = nullptr;
+  uint64_t stream_bytes = 0;
+  const uint64_t *frame_off = nullptr; // nullptr: no parse requested
+  int flags = 0;
+  uint64_t *body_off = nullptr; // n
+  uint32_t *body_len = nullptr; // n
+  uint32_t *hdr_crc = nullptr;  // n
+  uint8_t *pre = nullptr;       // n
+};
+// The stamp side of a call: frame i's body offset / effective length and its
+// verdict (the bounds and the cap, rpc_async.c:499-501), then the 12-byte
+// big-endian header of every OK frame (rpc_async.c:521-530: htons / htonl).
+struct FramesStamp {
+  uint8_t *stream = nullptr;
+  uint64_t stream_bytes = 0;
+  const uint64_t *frame_off = nullptr; // nullptr: no stamp requested
+  const uint32_t *body_len = nullptr;
+  int flags = 0;
+  uint16_t version = 0, type = 0;
+  uint64_t *body_off = nullptr; // n
+  uint32_t *len_eff = nullptr;  // n
+  uint8_t *pre = nullptr; // n; the verdict: OK (stamped), TOO_LARGE or MALFORMED
+};
+
+// ---- workspace -------------------------------------------------------------
+// The arrays of an n-frame verify and of an n-frame stamp in pool workspace,
+// over a WsLayout (workspace.h) or anything with its take<T>(count).  crc: the
+// body CRCs (n), which are no field of either struct.
+template <class Layout> inline void verify_ws_layout(Layout &w, FramesParse &p, uint32_t *&crc, uint64_t n) {
+  p.body_off = w.template take<uint64_t>(n);
+  p.body_len = w.template take<uint32_t>(n);
+  p.hdr_crc = w.template take<uint32_t>(n);
+  crc = w.template take<uint32_t>(n); // (reserved also when the caller's d_crc takes its place)
+  p.pre = w.template take<uint8_t>(n);
+}
+template <class Layout> inline void stamp_ws_layout(Layout &w, FramesStamp &p, uint32_t *&crc, uint64_t n) {
+  p.body_off = w.template take<uint64_t>(n);
+  p.len_eff = w.template take<uint32_t>(n);
+  crc = w.template take<uint32_t>(n);
+  p.pre = w.template take<uint8_t>(n); // (reserved also when the caller's d_verdict takes its place)
+}
+
+#if defined(__HIPCC__)
 __device__ __forceinline__ uint32_t be32(const uint8_t *p) {
   return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
 }
@@ -21,18 +70,6 @@ __device__ __forceinline__ bool inside(uint64_t off, uint64_t len, uint64_t byte
   return off <= bytes && len <= bytes - off;
 }
 
-// The header parse of a verify call: frame i's body offset / effective length,
-// header crc32 and verdict so far.
-struct FramesParse {
-  const uint8_t *stream = nullptr;
-  uint64_t stream_bytes = 0;
-  const uint64_t *frame_off = nullptr; // nullptr: no parse requested
-  int flags = 0;
-  uint64_t *body_off = nullptr;
-  uint32_t *body_len = nullptr;
-  uint32_t *hdr_crc = nullptr;
-  uint8_t *pre = nullptr;
-};
 // The reference's decision order for a received header: type (rpc_server_main.c:172
 // PING, rpc_async.c:303 PONG), then the body_len cap (rpc_server_main.c:189,
 // rpc_async.c:312), then the body is read and its CRC checked
@@ -80,24 +117,6 @@ __device__ __forceinline__ FrameBody frames_parse_one(const FramesParse &p, uint
   return FrameBody{boff, len};
 }
 
-// Reads each header (as rpc_server_main.c:165-169 does with ntohs/ntohl) and
-// applies the reference's type / cap / bounds rules (frames.hip): the body
-// offset and effective length (0 when the body is not read), the header crc32
-// and the verdict so far (RPC_FRAME_* or kFramePending).
-// The stamp side of a call: frame i's body offset / effective length and its
-// verdict (the bounds and the cap, rpc_async.c:499-501), then the 12-byte
-// big-endian header of every OK frame (rpc_async.c:521-530: htons / htonl).
-struct FramesStamp {
-  uint8_t *stream = nullptr;
-  uint64_t stream_bytes = 0;
-  const uint64_t *frame_off = nullptr; // nullptr: no stamp requested
-  const uint32_t *body_len = nullptr;
-  int flags = 0;
-  uint16_t version = 0, type = 0;
-  uint64_t *body_off = nullptr;
-  uint32_t *len_eff = nullptr;
-  uint8_t *pre = nullptr; // the verdict: OK (stamped), TOO_LARGE or MALFORMED
-};
 __device__ __forceinline__ FrameBody frames_stamp_prep_one(const FramesStamp &p, uint64_t i) {
   const uint64_t off = p.frame_off[i];
   const uint32_t bl = p.body_len[i];
@@ -132,6 +151,10 @@ __device__ __forceinline__ void frames_stamp_one(const FramesStamp &p, uint64_t 
   put_be32(h + 8, crc);
 }
 
+// Reads each header (as rpc_server_main.c:165-169 does with ntohs/ntohl) and
+// applies the reference's type / cap / bounds rules (frames.hip): the body
+// offset and effective length (0 when the body is not read), the header crc32
+// and the verdict so far (RPC_FRAME_* or kFramePending).
 hipError_t launch_frames_parse(const uint8_t *stream, uint64_t stream_bytes, const uint64_t *frame_off, uint64_t n,
                                int flags, uint64_t *body_off, uint32_t *body_len, uint32_t *hdr_crc, uint8_t *pre,
                                hipStream_t s);
@@ -143,5 +166,6 @@ hipError_t launch_frames_compare(const uint32_t *crc, const uint32_t *expected, 
 // every OK frame (frames_stamp_one).
 hipError_t launch_frames_stamp_prep(const FramesStamp &p, uint64_t n, hipStream_t s);
 hipError_t launch_frames_stamp(const FramesStamp &p, const uint32_t *crc, uint64_t n, hipStream_t s);
+#endif
 
 } // namespace rpccrc

@@ -444,8 +444,7 @@ ROUTE_HD uint8_t args_one(Body &body, uint32_t len, uint32_t base, const Schema 
   return defer ? kArgsDefer : kArgsOk;
 }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_args.hip) ----------------------------------------------
+// ---- the call (frames_args.hip; no workspace) -----------------------------------
 struct ArgsArgs {
   const uint8_t *bodies = nullptr;
   uint64_t bodies_bytes = 0;
@@ -468,6 +467,7 @@ struct ArgsArgs {
   uint8_t *status = nullptr;
   int32_t *reply_status = nullptr;
 };
+#if defined(__HIPCC__)
 hipError_t launch_frames_args(const ArgsArgs &a, hipStream_t s);
 #endif
 

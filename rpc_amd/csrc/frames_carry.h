@@ -85,8 +85,7 @@ PACK_HD PackPiece carry_piece(const Src &src, uint64_t s0, const PackSpan &ps) {
   return p;
 }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_carry.hip) ------------------------------------------
+// ---- the call (frames_carry.hip) ---------------------------------------------
 struct CarryArgs {
   const uint8_t *stream = nullptr;
   uint64_t stream_bytes = 0;
@@ -110,6 +109,17 @@ struct CarryArgs {
   uint64_t *tail = nullptr;     // nconn: CarryPlan.tail
   uint64_t *scan_tmp = nullptr; // scan_tmp_words(nconn)
 };
+// The long route's arrays in pool workspace (as pack_ws_layout); a.nconn is set.
+template <class Layout> inline void carry_ws_layout(Layout &w, CarryArgs &a, size_t tmp_words) {
+  a.cnt = w.template take<uint64_t>(a.nconn);
+  a.offs = w.template take<uint64_t>(a.nconn + 1);
+  a.src = w.template take<uint64_t>(a.nconn);
+  a.dst = w.template take<uint64_t>(a.nconn);
+  a.tail = w.template take<uint64_t>(a.nconn);
+  a.scan_tmp = w.template take<uint64_t>(tmp_words);
+}
+
+#if defined(__HIPCC__)
 // One launch: rule, copy, next round's connections (room <= kCarryShortRoom).
 hipError_t launch_frames_carry_short(const CarryArgs &a, hipStream_t s);
 // Plan pass, exclusive scan, chunk kernel.

@@ -16,6 +16,7 @@
 // Everything here is plain inline code with no HIP types, shared by the kernels
 // (frames_pack.hip) and the CPU emulator (tests/cpu_emu/pack_emu.cpp).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -303,8 +304,7 @@ PACK_HD uint64_t pack_conn_begin(const Off &off, const uint64_t *conn_first, uin
   return off(f < n ? f : n);
 }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_pack.hip) -----------------------------------------
+// ---- the call (frames_pack.hip) ---------------------------------------------
 struct PackArgs {
   const uint8_t *bodies = nullptr;
   uint64_t bodies_bytes = 0;
@@ -333,6 +333,19 @@ struct PackArgs {
   uint8_t *pre = nullptr;      // n: provisional verdicts
   uint64_t *scan_tmp = nullptr; // scan_tmp_words(n)
 };
+// Its arrays in pool workspace, over a WsLayout (workspace.h) or anything with
+// its take<T>(count); a.n is set.
+template <class Layout> inline void pack_ws_layout(Layout &w, PackArgs &a, size_t tmp_words) {
+  a.sizes = w.template take<uint64_t>(a.n);
+  a.src_off = w.template take<uint64_t>(a.n);
+  a.offs = w.template take<uint64_t>(a.n + 1);
+  a.scan_tmp = w.template take<uint64_t>(tmp_words);
+  a.src_len = w.template take<uint32_t>(a.n);
+  a.crc = w.template take<uint32_t>(a.n); // (reserved also when the caller's d_crc takes its place)
+  a.pre = w.template take<uint8_t>(a.n);
+}
+
+#if defined(__HIPCC__)
 // Size pass and exclusive scan: everything the CRC pass needs.
 hipError_t launch_frames_pack_layout(const PackArgs &a, hipStream_t s);
 // Pack kernel (when a.out is set; a.crc must hold the CRCs) and the finish pass.

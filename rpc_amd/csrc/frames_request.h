@@ -210,31 +210,7 @@ PACK_HD PackPiece request_piece(const Off &off, const Ent &ent, const Tab &tab, 
   return splice_piece(RequestSplice<Ent, Tab, Src>{ent, tab, src, out_cap}, off, src_of, lo, hi, x0, x1, b0);
 }
 
-// ---- workspace -------------------------------------------------------------------
-// The call's arrays in pool workspace, over a WsLayout (workspace.h) or anything
-// with its take<T>(count): the reply's, a 32-bit meta word, and one word per
-// table name.
-struct RequestWs {
-  uint64_t *sizes;     // n
-  uint64_t *src_off;   // n
-  uint64_t *offs;      // n + 1
-  uint64_t *scan_tmp;  // tmp_words
-  uint32_t *meta;      // n
-  uint32_t *name_word; // kRequestMaxMethods
-};
-template <class Layout> inline RequestWs request_ws_layout(Layout &w, uint64_t n, size_t tmp_words) {
-  RequestWs r;
-  r.sizes = w.template take<uint64_t>(n);
-  r.src_off = w.template take<uint64_t>(n);
-  r.offs = w.template take<uint64_t>(n + 1);
-  r.scan_tmp = w.template take<uint64_t>(tmp_words);
-  r.meta = w.template take<uint32_t>(n);
-  r.name_word = w.template take<uint32_t>(kRequestMaxMethods);
-  return r;
-}
-
-#if defined(__HIPCC__)
-// ---- device side (frames_request.hip) ------------------------------------------
+// ---- the call (frames_request.hip) ---------------------------------------------
 struct RequestArgs {
   const uint16_t *method = nullptr;
   const uint32_t *id = nullptr;
@@ -267,6 +243,18 @@ struct RequestArgs {
   uint32_t *name_word = nullptr; // kRequestMaxMethods: request_name_word of each name
   uint64_t *scan_tmp = nullptr;  // scan_tmp_words(n)
 };
+// Its arrays in pool workspace (as pack_ws_layout): the reply's, a 32-bit meta
+// word, and one word per table name.  a.n is set.
+template <class Layout> inline void request_ws_layout(Layout &w, RequestArgs &a, size_t tmp_words) {
+  a.sizes = w.template take<uint64_t>(a.n);
+  a.src_off = w.template take<uint64_t>(a.n);
+  a.offs = w.template take<uint64_t>(a.n + 1);
+  a.scan_tmp = w.template take<uint64_t>(tmp_words);
+  a.meta = w.template take<uint32_t>(a.n);
+  a.name_word = w.template take<uint32_t>(kRequestMaxMethods);
+}
+
+#if defined(__HIPCC__)
 // Table pass, size pass, exclusive scan, request kernel (when a.out is set),
 // finish pass.
 hipError_t launch_frames_request(const RequestArgs &a, hipStream_t s);

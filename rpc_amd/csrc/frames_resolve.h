@@ -20,6 +20,7 @@
 // Everything here is plain inline code with no HIP types, shared by the kernels
 // (frames_resolve.hip) and the CPU emulator (tests/cpu_emu/resolve_emu.cpp).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "frames_route.h"
@@ -116,8 +117,7 @@ ROUTE_HD uint8_t resolve_final(uint32_t slot_entry, uint32_t entry) {
   return slot_entry == entry ? kResolveMatched : kResolveDuplicate;
 }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_resolve.hip) ----------------------------------------
+// ---- the call (frames_resolve.hip) -------------------------------------------
 struct ResolveArgs {
   const uint8_t *bodies = nullptr;
   uint64_t bodies_bytes = 0;
@@ -141,6 +141,23 @@ struct ResolveArgs {
   uint64_t *offs = nullptr;     // npending + 1: the exclusive scan
   uint64_t *scan_tmp = nullptr; // scan_tmp_words(npending)
 };
+// The join's arrays in pool workspace, over a WsLayout (workspace.h) or anything
+// with its take<T>(count), for a call with npending > 0.  Set: a.n, a.npending,
+// a.bits, a.open, and a.slot / a.slot_entry where the caller gave them -- where
+// it did not, workspace stands in (a measuring pass leaves them nullptr, so the
+// carving pass over the same `a` takes the same arrays).
+template <class Layout> inline void resolve_ws_layout(Layout &w, ResolveArgs &a, size_t tmp_words) {
+  if (a.open) {
+    a.flags = w.template take<uint64_t>(a.npending);
+    a.offs = w.template take<uint64_t>((uint64_t)a.npending + 1);
+    a.scan_tmp = w.template take<uint64_t>(tmp_words);
+  }
+  a.cells = w.template take<uint32_t>((uint64_t)1 << a.bits);
+  if (!a.slot_entry) a.slot_entry = w.template take<uint32_t>(a.npending);
+  if (!a.slot && a.n) a.slot = w.template take<uint32_t>(a.n);
+}
+
+#if defined(__HIPCC__)
 // Table pass, resolve kernel, finish pass [-> exclusive scan -> compaction].
 hipError_t launch_frames_resolve(const ResolveArgs &a, hipStream_t s);
 #endif

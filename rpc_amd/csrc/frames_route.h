@@ -21,6 +21,7 @@
 // Everything here is plain inline code with no HIP types, shared by the kernels
 // (frames_route.hip) and the CPU emulator (tests/cpu_emu/route_emu.cpp).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -409,8 +410,7 @@ ROUTE_HD uint32_t route_popc64(uint64_t x) {
 }
 ROUTE_HD uint32_t route_wave_rank(uint64_t same, uint32_t lane) { return route_popc64(same & ((1ull << lane) - 1ull)); }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_route.hip) ------------------------------------------
+// ---- the call (frames_route.hip) ---------------------------------------------
 struct RouteArgs {
   const uint8_t *bodies = nullptr;
   uint64_t bodies_bytes = 0;
@@ -434,6 +434,17 @@ struct RouteArgs {
   uint64_t *scan_tmp = nullptr; // scan_tmp_words(buckets x workgroups)
 };
 inline uint64_t route_workgroups(uint64_t n) { return (n + kRouteEntries - 1) / kRouteEntries; }
+inline uint64_t route_cells(const RouteArgs &a) { return (uint64_t)route_buckets(a.nmethods) * route_workgroups(a.n); }
+// The grouping passes' arrays in pool workspace, over a WsLayout (workspace.h)
+// or anything with its take<T>(count); a.n and a.nmethods are set.
+template <class Layout> inline void route_ws_layout(Layout &w, RouteArgs &a, size_t tmp_words) {
+  a.counts = w.template take<uint64_t>(route_cells(a));
+  a.offs = w.template take<uint64_t>(route_cells(a) + 1);
+  a.scan_tmp = w.template take<uint64_t>(tmp_words);
+  a.bucket = w.template take<uint16_t>(a.n);
+}
+
+#if defined(__HIPCC__)
 // The route kernel, then (with a.order) count, exclusive scan, scatter.
 hipError_t launch_frames_route(const RouteArgs &a, hipStream_t s);
 #endif

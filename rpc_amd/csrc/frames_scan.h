@@ -22,6 +22,7 @@
 // (frames_scan.hip) and the CPU emulator (tests/cpu_emu/scan_emu.cpp), which
 // instantiates it with small tiles and groups as well.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -178,8 +179,7 @@ SCAN_HD uint64_t scan_find_conn(const uint64_t *tbase, uint64_t nconn, uint64_t 
   return lo - 1;
 }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_scan.hip) -----------------------------------------
+// ---- the call (frames_scan.hip) ---------------------------------------------
 struct ScanArgs {
   const uint8_t *stream = nullptr;
   uint64_t stream_bytes = 0;
@@ -211,6 +211,33 @@ struct ScanArgs {
   uint16_t *maps[kScanMaxLevels + 1] = {};  // level l: ceil(tile_cap / G^l) maps
   uint16_t *entry[kScanMaxLevels + 2] = {}; // level l: as many resolved entries
 };
+// The tiled route's arrays in pool workspace, over a WsLayout (workspace.h) or
+// anything with its take<T>(count); a.nconn, a.tile_cap and a.levels are set.
+template <class Layout> inline void scan_tiled_ws_layout(Layout &w, ScanArgs &a) {
+  a.conn_tiles = w.template take<uint64_t>(a.nconn);
+  a.tbase = w.template take<uint64_t>(a.nconn + 1);
+  a.nt_live = w.template take<uint64_t>(32); // (a 256-byte line of its own)
+  a.tconn = w.template take<uint32_t>(a.tile_cap);
+  a.tile_cnt = w.template take<uint64_t>(a.tile_cap);
+  a.tpre = w.template take<uint64_t>(a.tile_cap + 1);
+  for (int l = 0; l < a.levels; ++l) {
+    const uint64_t nl = scan_level_count<kScanGroup>(a.tile_cap, (uint32_t)l);
+    a.maps[l] = w.template take<uint16_t>(nl * kScanMapLen);
+    a.entry[l] = w.template take<uint16_t>(nl);
+  }
+}
+// Every route's arrays; a.nconn and a.frame_cap are set.  reach: the fused
+// call's first_close (nconn; the reach pass's, no field of `a`); own_conn: the
+// reach pass's frame_conn where the caller gave none.
+template <class Layout>
+inline void scan_ws_layout(Layout &w, ScanArgs &a, size_t tmp_words, bool reach, bool own_conn, uint64_t *&first_close) {
+  a.conn_cnt = w.template take<uint64_t>(a.nconn);
+  a.scan_tmp = w.template take<uint64_t>(tmp_words);
+  if (reach) first_close = w.template take<uint64_t>(a.nconn);
+  if (own_conn) a.frame_conn = w.template take<uint32_t>(a.frame_cap);
+}
+
+#if defined(__HIPCC__)
 // (scan_tmp_words(n), the words of scan_tmp a scan over n words needs: excl_scan.h)
 // Levels L for a workspace of tile_cap tiles (see ScanArgs::levels).
 int scan_levels_for(uint64_t tile_cap);

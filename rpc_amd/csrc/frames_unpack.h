@@ -132,8 +132,7 @@ PACK_HD PackPiece unpack_piece(const Off &off, const SrcOf &src_of, const Src &s
   return p;
 }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_unpack.hip) ---------------------------------------
+// ---- the call (frames_unpack.hip) -------------------------------------------
 struct UnpackArgs {
   const uint8_t *stream = nullptr;
   uint64_t stream_bytes = 0;
@@ -160,6 +159,17 @@ struct UnpackArgs {
   uint8_t *pre = nullptr;       // n: provisional verdicts
   uint64_t *scan_tmp = nullptr; // scan_tmp_words(n)
 };
+// Its arrays in pool workspace (as pack_ws_layout); a.n is set.
+template <class Layout> inline void unpack_ws_layout(Layout &w, UnpackArgs &a, size_t tmp_words) {
+  a.sizes = w.template take<uint64_t>(a.n);
+  a.src_off = w.template take<uint64_t>(a.n);
+  a.offs = w.template take<uint64_t>(a.n + 1);
+  a.scan_tmp = w.template take<uint64_t>(tmp_words);
+  a.ver = w.template take<uint16_t>(a.n);
+  a.pre = w.template take<uint8_t>(a.n);
+}
+
+#if defined(__HIPCC__)
 // Size pass, exclusive scan, unpack kernel (when a.out is set), finish pass.
 hipError_t launch_frames_unpack(const UnpackArgs &a, hipStream_t s);
 #endif

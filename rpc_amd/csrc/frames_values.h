@@ -519,8 +519,7 @@ PACK_HD PackPiece values_piece(const Off &off, const Ent &ent, const SrcOf &src_
   return splice_piece(ValuesSplice<Ent, Schema, Src>{ent, sc, strings, texts}, off, src_of, lo, hi, x0, x1, b0);
 }
 
-#if defined(__HIPCC__)
-// ---- device side (frames_values.hip) ------------------------------------------------
+// ---- the call (frames_values.hip) ---------------------------------------------------
 struct ValuesArgs {
   int form = 0;
   const uint8_t *mode = nullptr;   // nullptr: ENCODE for all
@@ -568,6 +567,25 @@ struct ValuesArgs {
   uint32_t *long_len = nullptr, *long_entry = nullptr, *long_bad = nullptr; // items each
   uint64_t *scan_tmp = nullptr;           // scan_tmp_words(items)
 };
+// Its arrays in pool workspace (as pack_ws_layout); a.n and a.items are set.
+template <class Layout> inline void values_ws_layout(Layout &w, ValuesArgs &a, size_t tmp_words) {
+  a.sizes = w.template take<uint64_t>(a.items);
+  a.src_off = w.template take<uint64_t>(a.items);
+  a.offs = w.template take<uint64_t>(a.items + 1);
+  a.scan_tmp = w.template take<uint64_t>(tmp_words);
+  a.text0 = w.template take<uint64_t>(a.items);
+  a.text1 = w.template take<uint64_t>(a.items);
+  a.text2 = w.template take<uint64_t>(a.items);
+  a.long_off = w.template take<uint64_t>(a.items);
+  a.meta = w.template take<uint32_t>(a.items);
+  a.long_len = w.template take<uint32_t>(a.items);
+  a.long_entry = w.template take<uint32_t>(a.items);
+  a.long_bad = w.template take<uint32_t>(a.items);
+  a.long_count = w.template take<uint32_t>(1);
+  a.pre = w.template take<uint8_t>(a.n);
+}
+
+#if defined(__HIPCC__)
 // Size pass, the grid's scan of very long strings, exclusive scan, values kernel
 // (when a.out is set), finish pass.
 hipError_t launch_frames_values(const ValuesArgs &a, hipStream_t s);

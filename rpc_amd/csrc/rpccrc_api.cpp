@@ -1,4 +1,7 @@
-// rpc_amd/csrc/rpccrc_api.cpp -- C-ABI host layer of librpccrc (include/rpccrc.h).
+// rpc_amd/csrc/rpccrc_api.cpp -- C-ABI host layer of librpccrc (include/rpccrc.h):
+// the CRC calls, the pools, the drop-in service, the host pipelines and the test
+// hooks.  The rpc_frames_* entry points are in frames_api.cpp; what the two
+// files share is declared in host_core.h.
 //
 // Owns per-device state, built once per device with std::call_once so the
 // drop-in calls stay thread-safe without an init call (SURVEY.md 8b
@@ -35,21 +38,9 @@
 #include "crc32_layout.h"
 #include "crc32_service_math.h"
 #include "frames.h"
-#include "frames_args.h"
-#include "frames_carry.h"
-#include "frames_pack.h"
-#include "frames_scan.h"
-#include "frames_reply.h"
-#include "frames_request.h"
-#include "frames_values.h"
-#include "frames_resolve.h"
-#include "frames_route.h"
-#include "frames_unpack.h"
+#include "host_core.h"
 
 namespace rpccrc {
-namespace {
-
-constexpr int kMaxDevices = 64;
 
 int map_hip(hipError_t e) {
   if (e == hipSuccess) return RPCCRC_OK;
@@ -59,140 +50,11 @@ int map_hip(hipError_t e) {
   return RPCCRC_EIO;
 }
 
-#define RPCCRC_TRY(expr)                      \
-  do {                                        \
-    const hipError_t _e = (expr);             \
-    if (_e != hipSuccess) return map_hip(_e); \
-  } while (0)
+namespace {
 
-// ---- pools -----------------------------------------------------------------
+constexpr int kMaxDevices = 64;
 
-// A cached block of device memory (or pinned host memory) lent to one call at
-// a time.  `ev` is recorded on the stream of the block's last use when the
-// call returns it.  The next borrower orders itself after that use: a device
-// block through hipStreamWaitEvent on its own stream (no host wait, and valid
-// even if the earlier stream has been destroyed since -- the event outlives
-// it), a pinned block through hipEventSynchronize (the host is about to write
-// it).  Replaces per-call hipMallocAsync/hipFreeAsync, whose free blocked the
-// calling thread until the GPU reached it (profiles/r01h_*), and the r01
-// per-thread cache that hipFree'd on every stream switch.
-struct Block {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-
-class BlockPool {
- public:
-  BlockPool(bool pinned, size_t keep) : pinned_(pinned), keep_(keep) {}
-
-  int acquire(size_t bytes, hipStream_t s, Block *out) {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      int best = -1;
-      for (int i = 0; i < (int)free_.size(); ++i)
-        if (free_[i].cap >= bytes && (best < 0 || free_[i].cap < free_[best].cap)) best = i;
-      if (best >= 0) {
-        *out = free_[best];
-        free_.erase(free_.begin() + best);
-        cached_ -= out->cap;
-      }
-    }
-    if (out->p) {
-      if (out->used) RPCCRC_TRY(pinned_ ? hipEventSynchronize(out->ev) : hipStreamWaitEvent(s, out->ev, 0));
-      return RPCCRC_OK;
-    }
-    size_t cap = pinned_ ? (64u << 10) : (1u << 20);
-    while (cap < bytes) cap <<= 1;
-    Block b;
-    hipError_t e = pinned_ ? hipHostMalloc(&b.p, cap, hipHostMallocDefault) : hipMalloc(&b.p, cap);
-    if (e != hipSuccess) {
-      b.p = nullptr;
-      return map_hip(e);
-    }
-    e = hipEventCreateWithFlags(&b.ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-      (void)(pinned_ ? hipHostFree(b.p) : hipFree(b.p));
-      return map_hip(e);
-    }
-    b.cap = cap;
-    *out = b;
-    return RPCCRC_OK;
-  }
-
-  // Returns the block after the call has enqueued its last use on stream s.
-  // recorded: the call's last kernel already recorded b.ev as its completion
-  // signal (hipExtLaunchKernel stopEvent), so no marker packet is needed here.
-  void release(Block &b, hipStream_t s, bool recorded = false) {
-    if (!b.p) return;
-    b.used = recorded || hipEventRecord(b.ev, s) == hipSuccess;
-    if (!b.used) (void)hipStreamSynchronize(s); // no event: make the block idle now
-    std::vector<Block> evict;
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      free_.push_back(b);
-      cached_ += b.cap;
-      // Over the keep limit: drop the largest idle blocks (rare; e.g. after a
-      // one-off huge batch).
-      while (cached_ > keep_ && !free_.empty()) {
-        auto it = std::max_element(free_.begin(), free_.end(),
-                                   [](const Block &x, const Block &y) { return x.cap < y.cap; });
-        cached_ -= it->cap;
-        evict.push_back(*it);
-        free_.erase(it);
-      }
-    }
-    for (Block &x : evict) {
-      if (x.used) (void)hipEventSynchronize(x.ev);
-      (void)(pinned_ ? hipHostFree(x.p) : hipFree(x.p));
-      (void)hipEventDestroy(x.ev);
-    }
-    b = Block();
-  }
-
- private:
-  std::mutex mu_;
-  std::vector<Block> free_;
-  size_t cached_ = 0;
-  const bool pinned_;
-  const size_t keep_;
-};
-
-// A block borrowed for the duration of one call (returned by the destructor,
-// after the call has enqueued all its work on `s`).
-struct Lease {
-  BlockPool *pool = nullptr;
-  Block b;
-  hipStream_t s = nullptr;
-  bool recorded = false; // the call's last launch recorded b.ev (done_event())
-  Lease() = default;
-  Lease(const Lease &) = delete;
-  Lease &operator=(const Lease &) = delete;
-  ~Lease() {
-    if (pool) pool->release(b, s, recorded);
-  }
-  // The block's event, for the call's LAST launch on s to record as its own
-  // completion (then set `recorded`).
-  hipEvent_t done_event() const { return b.ev; }
-  int get(BlockPool *p, size_t bytes, hipStream_t stream) {
-    pool = p;
-    s = stream;
-    return p->acquire(bytes, stream, &b);
-  }
-  uint8_t *ptr() const { return static_cast<uint8_t *>(b.p); }
-  // A block for the arrays that layout(WsLayout &) takes, and slack bytes behind
-  // them: a measuring pass sizes the lease, the same function then carves it.
-  template <class F> int get(BlockPool *p, hipStream_t stream, F &&layout, size_t slack = 0) {
-    WsLayout m;
-    layout(m);
-    if (!m.ok()) return RPCCRC_EINVAL;
-    if (const int rc = get(p, m.used() + slack, stream)) return rc;
-    WsLayout w(ptr(), m.used());
-    layout(w);
-    return w.ok() ? RPCCRC_OK : RPCCRC_EINVAL;
-  }
-};
+// ---- pools (BlockPool and Lease: host_core.h) --------------------------------
 
 // Two-word device counters for the rows kernel's tail stealing (crc32_rows.h
 // kStealAhead).  A launch leases one; the launch's last workgroup resets it
@@ -360,7 +222,9 @@ struct Service {
   bool ok = false;
 };
 
-struct DeviceCtx {
+} // namespace
+
+struct DeviceCtx { // (named in host_core.h)
   int device = -1;
   int cus = 0;
   uint4 *img = nullptr; // LDS table image (rows kernel layout, 155 KiB)
@@ -399,6 +263,9 @@ struct DeviceCtx {
   uint32_t *probe_sink = nullptr;
   std::once_flag probe_once;
 };
+BlockPool *ws_pool(const DeviceCtx &c) { return c.ws; }
+
+namespace {
 
 DeviceCtx g_dev[kMaxDevices];
 std::once_flag g_once[kMaxDevices];
@@ -407,7 +274,6 @@ std::once_flag g_once[kMaxDevices];
 std::atomic<int> g_nontemporal{1}; // streamed once: non-temporal loads (measured faster)
 std::atomic<int> g_max_blocks{0};
 std::atomic<int> g_ragged_path{RPCCRC_RAGGED_AUTO};
-std::atomic<int> g_scan_path{RPCCRC_SCAN_AUTO};
 // Large-body chunk (rpc_crc32_device_large, chunk_bytes = 0).  C4 per call
 // (profiles/r01c4_*): 4 KiB 697 us (rows kernel fastest, combine 27 us),
 // 16 KiB 673 us, 64 KiB 689 us (each wave streams its own 64 KiB).
@@ -570,10 +436,12 @@ int get_ctx(DeviceCtx **out) {
 
 // The same for an asynchronous call: RPCCRC_EIO while the device error word
 // holds an uncleared error (DeviceCtx::err).
+} // namespace
 int get_async_ctx(DeviceCtx **out) {
   const int rc = get_ctx(out);
   return rc ? rc : device_error(**out);
 }
+namespace {
 
 #ifdef RPCCRC_TEST_HOOKS
 long env_count(const char *name) { // NAME=K: a test hook's budget of K uses
@@ -723,29 +591,7 @@ int items(const DeviceCtx &c, const uint8_t *base, const uint64_t *offsets, cons
 //    batch over a 4 KiB-aligned base may take the route's span mode (BigRoute).
 //  * cmp (frames verify): in route-all mode the fold writes the verdicts too
 //    and compared is set (the caller then skips its compare launch).
-struct FramesCmp {
-  const uint32_t *expected;
-  const uint8_t *pre;
-  uint8_t *verdict;
-};
-struct RaggedCall {
-  const uint8_t *base; // the batch
-  const uint64_t *offsets;
-  const uint32_t *lengths;
-  uint64_t n;
-  uint32_t *out;
-  uint32_t mode = kModeFinal;
-  bool small_bodies = false; // hints
-  bool route = false;
-  uint32_t max_len = 0; // the caller's bound on every length (0: none)
-  uint64_t span_bytes = 0;
-  uint32_t *err = nullptr; // the launches' error word (as items())
-  const FramesCmp *cmp = nullptr; // frames hooks
-  const FramesParse *parse = nullptr;
-  const FramesStamp *stamp = nullptr;
-  bool compared = false; // results
-  bool stamped = false;
-};
+} // namespace
 int ragged(const DeviceCtx &c, RaggedCall &q, hipStream_t s) {
   const uint64_t n = q.n;
   const int path = g_ragged_path.load(std::memory_order_relaxed);
@@ -920,6 +766,7 @@ int ragged(const DeviceCtx &c, RaggedCall &q, hipStream_t s) {
   }
   return RPCCRC_OK;
 }
+namespace {
 
 // ---- large bodies: chunk expansion + combine --------------------------------
 
@@ -1640,132 +1487,12 @@ int host_gather(DeviceCtx &c, const uint8_t *base, const uint64_t *seg_offsets, 
   return rc;
 }
 
-bool frames_flags_ok(int flags) {
-  const int role = flags & (RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT);
-  return (flags & ~(RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT | RPC_FRAMES_LIFT_CAP)) == 0 &&
-         (role == RPC_FRAMES_SERVER || role == RPC_FRAMES_CLIENT);
-}
-
-// What rpc_frames_pack_device and rpc_frames_unpack_device ask of the arguments
-// they have in common.
-bool frames_layout_args_ok(uint64_t n, const uint8_t *d_out, uint64_t out_cap, const uint64_t *d_conn_first,
-                           uint64_t nconn, const uint64_t *d_conn_bytes_first) {
-  if (n >= 0xFFFFFFFFull) return false;
-  if (out_cap > 0 && !d_out) return false;
-  if (d_conn_bytes_first && !d_conn_first) return false;
-  return nconn == 0 || d_conn_first;
-}
-
-// Their empty batch: every offset is 0.
-int frames_layout_empty(uint64_t *d_total, uint64_t *d_conn_bytes_first, uint64_t nconn, hipStream_t s) {
-  if (d_total) RPCCRC_TRY(hipMemsetAsync(d_total, 0, 8, s));
-  if (d_conn_bytes_first) RPCCRC_TRY(hipMemsetAsync(d_conn_bytes_first, 0, (nconn + 1) * 8, s));
-  return RPCCRC_OK;
-}
 
 } // namespace
 } // namespace rpccrc
 
 using namespace rpccrc;
 
-// rpc_frames_scan_device, and with d_verdict the fused scan + verify + reach pass.
-static int frames_scan_common(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
-                              const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
-                              uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first,
-                              uint64_t *d_conn_consumed, uint8_t *d_conn_state, uint64_t *d_nframes, uint8_t *d_verdict,
-                              uint32_t *d_crc, bool fused, void *stream) {
-  if (!frames_flags_ok(flags)) return RPCCRC_EINVAL;
-  if (!d_nframes || !d_conn_first || nconn >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  if (frame_cap != 0 && !d_frame_offsets) return RPCCRC_EINVAL;
-  if (nconn != 0 && (!d_stream || !d_conn_off || !d_conn_len || !d_conn_consumed || !d_conn_state))
-    return RPCCRC_EINVAL;
-  if (fused && frame_cap != 0 && (!d_verdict || !d_stream || frame_cap >= 0xFFFFFFFFull)) return RPCCRC_EINVAL;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool reach = fused && frame_cap != 0 && nconn != 0;
-
-  ScanArgs a;
-  a.stream = d_stream;
-  a.stream_bytes = stream_bytes;
-  a.conn_off = d_conn_off;
-  a.conn_len = d_conn_len;
-  a.nconn = nconn;
-  a.flags = flags;
-  a.frame_off = d_frame_offsets;
-  a.frame_conn = d_frame_conn;
-  a.frame_cap = frame_cap;
-  a.conn_first = d_conn_first;
-  a.consumed = d_conn_consumed;
-  a.state = d_conn_state;
-  a.nframes = d_nframes;
-
-  // The tiled route: cap in force only, for connections longer than tiled_min.
-  // Connections inside the stream that do not overlap need at most
-  // stream_bytes / T + (one more per tiled connection) tiles; what does not
-  // fit the workspace walks serially.
-  const int path = g_scan_path.load(std::memory_order_relaxed);
-  uint64_t tile_cap = 0;
-  a.tiled_min = path == RPCCRC_SCAN_TILED ? kScanTile : kScanTiledMin;
-  if (nconn != 0 && path != RPCCRC_SCAN_SERIAL && !(flags & RPC_FRAMES_LIFT_CAP) && stream_bytes > a.tiled_min) {
-    uint64_t max_tiles = 1;
-    for (uint32_t i = 0; i <= kScanMaxLevels; ++i) max_tiles *= kScanGroup;
-    tile_cap = stream_bytes / kScanTile + std::min<uint64_t>(nconn, stream_bytes / a.tiled_min) + 1;
-    tile_cap = std::min(tile_cap, max_tiles);
-  }
-  Lease tiled;
-  if (tile_cap) {
-    const int L = scan_levels_for(tile_cap);
-    auto layout = [&](WsLayout &w) {
-      a.conn_tiles = w.take<uint64_t>(nconn);
-      a.tbase = w.take<uint64_t>(nconn + 1);
-      a.nt_live = w.take<uint64_t>(32); // (a 256-byte line of its own)
-      a.tconn = w.take<uint32_t>(tile_cap);
-      a.tile_cnt = w.take<uint64_t>(tile_cap);
-      a.tpre = w.take<uint64_t>(tile_cap + 1);
-      for (int l = 0; l < L; ++l) {
-        const uint64_t nl = scan_level_count<kScanGroup>(tile_cap, (uint32_t)l);
-        a.maps[l] = w.take<uint16_t>(nl * kScanMapLen);
-        a.entry[l] = w.take<uint16_t>(nl);
-      }
-    };
-    WsLayout size;
-    layout(size);
-    if (!size.ok() || tiled.get(c->ws, size.used(), s) != RPCCRC_OK) {
-      tile_cap = 0; // no workspace: every connection walks serially (results identical)
-      (void)hipGetLastError(); // (the failed allocation's error is not the next launch's)
-    } else {
-      WsLayout w(tiled.ptr(), size.used());
-      layout(w);
-      if (!w.ok()) return RPCCRC_EINVAL;
-      a.levels = L;
-    }
-  }
-  a.tile_cap = tile_cap;
-
-  Lease base;
-  const size_t tmp_words = scan_tmp_words(std::max(nconn, tile_cap));
-  const bool own_conn = reach && !d_frame_conn;
-  uint64_t *first_close = nullptr;
-  // (nconn == 0 runs the same launches: no unit finds work, *d_nframes = 0,
-  // every entry of d_frame_offsets is padding)
-  auto base_layout = [&](WsLayout &w) {
-    a.conn_cnt = w.take<uint64_t>(nconn);
-    a.scan_tmp = w.take<uint64_t>(tmp_words);
-    if (reach) first_close = w.take<uint64_t>(nconn);
-    if (own_conn) a.frame_conn = w.take<uint32_t>(frame_cap);
-  };
-  if ((rc = base.get(c->ws, s, base_layout, 256))) return rc;
-  if ((rc = map_hip(launch_frames_scan(a, s)))) return rc;
-  if (!fused || frame_cap == 0) return RPCCRC_OK;
-  if ((rc = rpc_frames_verify_device(d_stream, stream_bytes, d_frame_offsets, frame_cap, flags, d_verdict, d_crc,
-                                     stream)))
-    return rc;
-  if (!reach) return RPCCRC_OK;
-  return map_hip(launch_frames_reach(a.frame_conn, frame_cap, d_nframes, nconn, first_close, d_verdict, d_crc,
-                                     d_conn_state, s));
-}
 
 extern "C" {
 
@@ -1889,624 +1616,6 @@ uint32_t rpc_crc32_update(uint32_t crc, const void *data, size_t len) {
   return crc32_combine(crc, rpc_crc32(data, len32), len32);
 }
 
-int rpc_frames_verify_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_frame_offsets,
-                             uint64_t n, int flags, uint8_t *d_verdict, uint32_t *d_crc, void *stream) {
-  if (!frames_flags_ok(flags)) return RPCCRC_EINVAL;
-  if (n == 0) return RPCCRC_OK;
-  if (!d_stream || !d_frame_offsets || !d_verdict || n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  FramesParse fp; // (launched by ragged(), or fused into the route's plan)
-  uint32_t *bcrc = nullptr;
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    fp.body_off = w.take<uint64_t>(n);
-    fp.body_len = w.take<uint32_t>(n);
-    fp.hdr_crc = w.take<uint32_t>(n);
-    bcrc = w.take<uint32_t>(n); // (reserved also when the caller's d_crc takes its place)
-    fp.pre = w.take<uint8_t>(n);
-  });
-  if (rc) return rc;
-  if (d_crc) bcrc = d_crc;
-  fp.stream = d_stream;
-  fp.stream_bytes = stream_bytes;
-  fp.frame_off = d_frame_offsets;
-  fp.flags = flags;
-  const FramesCmp cmp{fp.hdr_crc, fp.pre, d_verdict};
-  RaggedCall q{d_stream, fp.body_off, fp.body_len, n, bcrc};
-  q.small_bodies = true;
-  q.route = (flags & RPC_FRAMES_LIFT_CAP) != 0;
-  q.span_bytes = stream_bytes;
-  q.cmp = &cmp;
-  q.parse = &fp;
-  if ((rc = ragged(*c, q, s))) return rc;
-  if (q.compared) return RPCCRC_OK; // (route-all: the fold wrote the verdicts)
-  return map_hip(launch_frames_compare(bcrc, fp.hdr_crc, fp.pre, n, d_verdict, s));
-}
-
-int rpc_frames_stamp_device(uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_frame_offsets,
-                            const uint32_t *d_body_lens, uint64_t n, uint16_t version, uint16_t type, int flags,
-                            uint8_t *d_verdict, void *stream) {
-  if ((flags & ~(RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT | RPC_FRAMES_LIFT_CAP)) != 0) return RPCCRC_EINVAL;
-  if (n == 0) return RPCCRC_OK;
-  if (!d_stream || !d_frame_offsets || !d_body_lens || n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  FramesStamp st; // (the check launched by ragged(), or fused into the route's plan; the headers likewise)
-  uint32_t *bcrc = nullptr;
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    st.body_off = w.take<uint64_t>(n);
-    st.len_eff = w.take<uint32_t>(n);
-    bcrc = w.take<uint32_t>(n);
-    st.pre = w.take<uint8_t>(n); // (reserved also when the caller's d_verdict takes its place)
-  });
-  if (rc) return rc;
-  if (d_verdict) st.pre = d_verdict;
-  st.stream = d_stream;
-  st.stream_bytes = stream_bytes;
-  st.frame_off = d_frame_offsets;
-  st.body_len = d_body_lens;
-  st.flags = flags;
-  st.version = version;
-  st.type = type;
-  RaggedCall q{d_stream, st.body_off, st.len_eff, n, bcrc};
-  q.small_bodies = true;
-  q.route = (flags & RPC_FRAMES_LIFT_CAP) != 0;
-  q.span_bytes = stream_bytes;
-  q.stamp = &st;
-  if ((rc = ragged(*c, q, s))) return rc;
-  if (q.stamped) return RPCCRC_OK; // (route-all: the fold wrote the headers)
-  return map_hip(launch_frames_stamp(st, bcrc, n, s));
-}
-
-int rpc_frames_pack_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
-                           const uint32_t *d_body_lens, uint64_t n, const uint16_t *d_types, uint16_t type,
-                           const uint16_t *d_versions, uint16_t version, const uint64_t *d_conn_first, uint64_t nconn,
-                           int flags, uint8_t *d_out, uint64_t out_cap, uint64_t *d_frame_offsets, uint8_t *d_verdict,
-                           uint32_t *d_crc, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
-  if ((flags & ~(RPC_FRAMES_SERVER | RPC_FRAMES_CLIENT | RPC_FRAMES_LIFT_CAP)) != 0) return RPCCRC_EINVAL;
-  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
-  const bool no_data = !d_types && !pack_is_data(type); // heartbeats or nothing: no body is looked at
-  if (n > 0 && !no_data && (!d_body_lens || !d_body_offsets)) return RPCCRC_EINVAL;
-  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
-  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
-  const size_t tmp_words = scan_tmp_words(n);
-  PackArgs a;
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    a.sizes = w.take<uint64_t>(n);
-    a.src_off = w.take<uint64_t>(n);
-    a.offs = w.take<uint64_t>(n + 1);
-    a.scan_tmp = w.take<uint64_t>(tmp_words);
-    a.src_len = w.take<uint32_t>(n);
-    a.crc = w.take<uint32_t>(n); // (reserved also when the caller's d_crc takes its place)
-    a.pre = w.take<uint8_t>(n);
-  });
-  if (rc) return rc;
-  if (d_crc) a.crc = d_crc;
-  a.bodies = d_bodies;
-  a.bodies_bytes = bodies_bytes;
-  a.body_off = d_body_offsets;
-  a.body_len = d_body_lens;
-  a.n = n;
-  a.types = d_types;
-  a.versions = d_versions;
-  a.type = type;
-  a.version = version;
-  a.conn_first = d_conn_first;
-  a.nconn = nconn;
-  a.flags = flags;
-  a.out = d_out;
-  a.out_cap = out_cap;
-  a.frame_off = d_frame_offsets;
-  a.verdict = d_verdict;
-  a.conn_bytes_first = d_conn_bytes_first;
-  a.total = d_total;
-  if ((rc = map_hip(launch_frames_pack_layout(a, s)))) return rc;
-  // The CRCs, over the source bodies: the ragged call stamp makes (the length
-  // bound, the lifted-cap route), without its hooks.  A layout-only call that
-  // does not ask for them skips the pass; a batch that cannot hold a data
-  // frame has no body to read (every CRC is 0).
-  if (no_data || !d_bodies) { // (no source buffer: every body the CRC pass would read is empty)
-    RPCCRC_TRY(hipMemsetAsync(a.crc, 0, n * 4, s));
-  } else if (d_out || d_crc) {
-    RaggedCall q{d_bodies, a.src_off, a.src_len, n, a.crc};
-    q.small_bodies = true;
-    q.route = (flags & RPC_FRAMES_LIFT_CAP) != 0;
-    q.span_bytes = bodies_bytes;
-    if ((rc = ragged(*c, q, s))) return rc;
-  }
-  return map_hip(launch_frames_pack_write(a, s));
-}
-
-int rpc_frames_unpack_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_frame_offsets,
-                             const uint8_t *d_verdict, uint64_t n, const uint64_t *d_conn_first, uint64_t nconn,
-                             int flags, int nul, uint8_t *d_out, uint64_t out_cap, uint64_t *d_body_offsets,
-                             uint32_t *d_body_lens, uint16_t *d_reply_types, uint16_t *d_versions,
-                             uint8_t *d_verdict_out, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
-  if (!frames_flags_ok(flags)) return RPCCRC_EINVAL;
-  if (nul != 0 && nul != 1) return RPCCRC_EINVAL;
-  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
-  if (n > 0 && (!d_frame_offsets || !d_verdict)) return RPCCRC_EINVAL;
-  if (stream_bytes > 0 && !d_stream) return RPCCRC_EINVAL;
-  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
-  const size_t tmp_words = scan_tmp_words(n);
-  UnpackArgs a;
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    a.sizes = w.take<uint64_t>(n);
-    a.src_off = w.take<uint64_t>(n);
-    a.offs = w.take<uint64_t>(n + 1);
-    a.scan_tmp = w.take<uint64_t>(tmp_words);
-    a.ver = w.take<uint16_t>(n);
-    a.pre = w.take<uint8_t>(n);
-  });
-  if (rc) return rc;
-  a.stream = d_stream;
-  a.stream_bytes = stream_bytes;
-  a.frame_off = d_frame_offsets;
-  a.verdict_in = d_verdict;
-  a.n = n;
-  a.conn_first = d_conn_first;
-  a.nconn = nconn;
-  a.flags = flags;
-  a.nul = nul;
-  a.out = d_out;
-  a.out_cap = out_cap;
-  a.body_off = d_body_offsets;
-  a.body_len = d_body_lens;
-  a.reply_types = d_reply_types;
-  a.versions = d_versions;
-  a.verdict_out = d_verdict_out;
-  a.conn_bytes_first = d_conn_bytes_first;
-  a.total = d_total;
-  return map_hip(launch_frames_unpack(a, s));
-}
-
-int rpc_frames_carry_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
-                            const uint64_t *d_conn_len, const uint64_t *d_conn_consumed, const uint8_t *d_conn_state,
-                            uint64_t nconn, uint8_t *d_next, uint64_t next_bytes, const uint64_t *d_next_at,
-                            uint64_t room, const uint64_t *d_new_len, uint64_t *d_next_off, uint64_t *d_next_len,
-                            uint8_t *d_status, uint64_t *d_carried, void *stream) {
-  if (nconn >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  if (nconn > 0 && (!d_conn_off || !d_conn_len || !d_conn_consumed || !d_next_at || !d_next_off || !d_next_len))
-    return RPCCRC_EINVAL;
-  if (stream_bytes > 0 && !d_stream) return RPCCRC_EINVAL;
-  if (next_bytes > 0 && !d_next) return RPCCRC_EINVAL;
-  if (nconn == 0 && !d_carried) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d_carried) RPCCRC_TRY(hipMemsetAsync(d_carried, 0, 8, s)); // (the kernels add to it)
-  if (nconn == 0) return RPCCRC_OK;
-  CarryArgs a;
-  a.stream = d_stream;
-  a.stream_bytes = stream_bytes;
-  a.conn_off = d_conn_off;
-  a.conn_len = d_conn_len;
-  a.conn_consumed = d_conn_consumed;
-  a.conn_state = d_conn_state;
-  a.nconn = nconn;
-  a.next = d_next;
-  a.next_bytes = next_bytes;
-  a.next_at = d_next_at;
-  a.room = room;
-  a.new_len = d_new_len;
-  a.next_off = d_next_off;
-  a.next_len = d_next_len;
-  a.status = d_status;
-  a.carried = d_carried;
-  // No tail can be longer than room: up to the threshold a group of lanes walks
-  // a whole tail in one launch, and the long route's passes (plan, scan, chunks)
-  // are not launched -- the idea of max_len in rpc_crc32_device_batch_bounded.
-  if (room <= kCarryShortRoom) return map_hip(launch_frames_carry_short(a, s));
-  const size_t tmp_words = scan_tmp_words(nconn);
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    a.cnt = w.take<uint64_t>(nconn);
-    a.offs = w.take<uint64_t>(nconn + 1);
-    a.src = w.take<uint64_t>(nconn);
-    a.dst = w.take<uint64_t>(nconn);
-    a.tail = w.take<uint64_t>(nconn);
-    a.scan_tmp = w.take<uint64_t>(tmp_words);
-  });
-  if (rc) return rc;
-  return map_hip(launch_frames_carry_long(a, s));
-}
-
-int rpc_frames_route_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
-                            const uint32_t *d_body_lens, const uint16_t *d_reply_types, uint64_t n,
-                            const uint8_t *d_method_names, uint32_t method_bytes, const uint32_t *d_method_off,
-                            uint32_t nmethods, uint8_t *d_kind, uint16_t *d_method, uint32_t *d_id,
-                            uint32_t *d_params_off, uint32_t *d_params_len, uint32_t *d_order,
-                            uint32_t *d_group_first, void *stream) {
-  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  if (nmethods > RPC_ROUTE_MAX_METHODS || method_bytes > RPC_ROUTE_MAX_METHOD_BYTES) return RPCCRC_EINVAL;
-  if (n > 0 && (!d_body_offsets || !d_body_lens)) return RPCCRC_EINVAL;
-  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
-  if (nmethods > 0 && !d_method_off) return RPCCRC_EINVAL;
-  if (method_bytes > 0 && !d_method_names) return RPCCRC_EINVAL;
-  if ((d_order == nullptr) != (d_group_first == nullptr)) return RPCCRC_EINVAL;
-  if (n == 0 && !d_group_first) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) { // no entries: every group is empty
-    RPCCRC_TRY(hipMemsetAsync(d_group_first, 0, ((size_t)nmethods + 4) * 4, s));
-    return RPCCRC_OK;
-  }
-  RouteArgs a;
-  Lease wsl;
-  if (d_order) { // (without the order outputs none of the grouping passes is launched)
-    const uint64_t cells = (uint64_t)route_buckets(nmethods) * route_workgroups(n);
-    const size_t tmp_words = scan_tmp_words(cells);
-    rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-      a.counts = w.take<uint64_t>(cells);
-      a.offs = w.take<uint64_t>(cells + 1);
-      a.scan_tmp = w.take<uint64_t>(tmp_words);
-      a.bucket = w.take<uint16_t>(n);
-    });
-    if (rc) return rc;
-  }
-  a.bodies = d_bodies;
-  a.bodies_bytes = bodies_bytes;
-  a.body_off = d_body_offsets;
-  a.body_len = d_body_lens;
-  a.types = d_reply_types;
-  a.n = n;
-  a.names = d_method_names;
-  a.method_bytes = method_bytes;
-  a.method_off = d_method_off;
-  a.nmethods = nmethods;
-  a.kind = d_kind;
-  a.method = d_method;
-  a.id = d_id;
-  a.params_off = d_params_off;
-  a.params_len = d_params_len;
-  a.order = d_order;
-  a.group_first = d_group_first;
-  return map_hip(launch_frames_route(a, s));
-}
-
-int rpc_frames_args_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
-                           const uint32_t *d_body_lens, const uint8_t *d_kind, const uint16_t *d_method,
-                           const uint32_t *d_params_off, const uint32_t *d_params_len, uint64_t n,
-                           const uint32_t *d_param_first, uint32_t nmethods, const uint8_t *d_param_types,
-                           const uint32_t *d_param_name_off, uint32_t nparams, const uint8_t *d_param_names,
-                           uint32_t name_bytes, uint32_t width, uint64_t *d_slots, uint8_t *d_status,
-                           int32_t *d_reply_status, void *stream) {
-  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  if (nmethods > RPC_ROUTE_MAX_METHODS || nparams > RPC_ARGS_MAX_SCHEMA_PARAMS || name_bytes > RPC_ARGS_MAX_NAME_BYTES)
-    return RPCCRC_EINVAL;
-  if (width == 0 || width > RPC_ARGS_MAX_PARAMS) return RPCCRC_EINVAL;
-  if (n > 0 && (!d_body_offsets || !d_body_lens || !d_kind || !d_method || !d_params_off || !d_params_len))
-    return RPCCRC_EINVAL;
-  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
-  if (nmethods > 0 && !d_param_first) return RPCCRC_EINVAL;
-  if (nparams > 0 && (!d_param_types || !d_param_name_off)) return RPCCRC_EINVAL;
-  if (name_bytes > 0 && !d_param_names) return RPCCRC_EINVAL;
-  if (n == 0) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  const int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  ArgsArgs a;
-  a.bodies = d_bodies;
-  a.bodies_bytes = bodies_bytes;
-  a.body_off = d_body_offsets;
-  a.body_len = d_body_lens;
-  a.kind = d_kind;
-  a.method = d_method;
-  a.params_off = d_params_off;
-  a.params_len = d_params_len;
-  a.n = n;
-  a.param_first = d_param_first;
-  a.nmethods = nmethods;
-  a.param_types = d_param_types;
-  a.param_name_off = d_param_name_off;
-  a.nparams = nparams;
-  a.param_names = d_param_names;
-  a.name_bytes = name_bytes;
-  a.width = width;
-  a.slots = d_slots;
-  a.status = d_status;
-  a.reply_status = d_reply_status;
-  return map_hip(launch_frames_args(a, static_cast<hipStream_t>(stream)));
-}
-
-int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const int32_t *d_status,
-                            const uint16_t *d_reply_types, uint64_t n, const uint8_t *d_values, uint64_t values_bytes,
-                            const uint64_t *d_value_offsets, const uint32_t *d_value_lens, const uint64_t *d_conn_first,
-                            uint64_t nconn, uint8_t *d_out, uint64_t out_cap, uint64_t *d_body_offsets,
-                            uint32_t *d_body_lens, uint16_t *d_types_out, uint8_t *d_reply_status,
-                            uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
-  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
-  if (n > 0 && (!d_id || !d_value_offsets || !d_value_lens)) return RPCCRC_EINVAL;
-  if (values_bytes > 0 && !d_values) return RPCCRC_EINVAL;
-  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
-  const size_t tmp_words = scan_tmp_words(n);
-  ReplyArgs a;
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    a.sizes = w.take<uint64_t>(n);
-    a.src_off = w.take<uint64_t>(n);
-    a.offs = w.take<uint64_t>(n + 1);
-    a.scan_tmp = w.take<uint64_t>(tmp_words);
-    a.code = w.take<int32_t>(n);
-    a.meta = w.take<uint16_t>(n);
-  });
-  if (rc) return rc;
-  a.kind = d_kind;
-  a.id = d_id;
-  a.status = d_status;
-  a.reply_types = d_reply_types;
-  a.n = n;
-  a.values = d_values;
-  a.values_bytes = values_bytes;
-  a.value_off = d_value_offsets;
-  a.value_len = d_value_lens;
-  a.conn_first = d_conn_first;
-  a.nconn = nconn;
-  a.out = d_out;
-  a.out_cap = out_cap;
-  a.body_off = d_body_offsets;
-  a.body_len = d_body_lens;
-  a.types_out = d_types_out;
-  a.reply_status = d_reply_status;
-  a.conn_bytes_first = d_conn_bytes_first;
-  a.total = d_total;
-  return map_hip(launch_frames_reply(a, s));
-}
-
-int rpc_frames_values_device(int form, const uint8_t *d_mode, const int32_t *d_status, const uint16_t *d_method,
-                             const uint64_t *d_slots, uint32_t width, uint64_t n, const uint8_t *d_result_types,
-                             const uint32_t *d_param_first, uint32_t nmethods, const uint8_t *d_param_types,
-                             const uint32_t *d_param_name_off, uint32_t nparams, const uint8_t *d_param_names,
-                             uint32_t name_bytes, const uint8_t *d_strings, uint64_t strings_bytes,
-                             const uint64_t *d_str_base, const uint8_t *d_texts, uint64_t texts_bytes,
-                             const uint64_t *d_text_offsets, const uint32_t *d_text_lens, uint8_t *d_out,
-                             uint64_t out_cap, uint64_t *d_value_offsets, uint32_t *d_value_lens,
-                             uint8_t *d_values_status, int32_t *d_reply_status, uint32_t *d_ndefer, uint64_t *d_total,
-                             void *stream) {
-  if (form != RPC_VALUES_FORM_RESULT && form != RPC_VALUES_FORM_PARAMS) return RPCCRC_EINVAL;
-  if (!frames_layout_args_ok(n, d_out, out_cap, nullptr, 0, nullptr)) return RPCCRC_EINVAL;
-  if (width == 0 || width > RPC_ARGS_MAX_PARAMS) return RPCCRC_EINVAL;
-  if (nmethods > RPC_ROUTE_MAX_METHODS) return RPCCRC_EINVAL;
-  if (n > 0 && (!d_method || !d_slots)) return RPCCRC_EINVAL;
-  const bool params = form == RPC_VALUES_FORM_PARAMS;
-  if (params) {
-    if (nparams > RPC_ARGS_MAX_SCHEMA_PARAMS || name_bytes > RPC_ARGS_MAX_NAME_BYTES) return RPCCRC_EINVAL;
-    if (nmethods > 0 && !d_param_first) return RPCCRC_EINVAL;
-    if (nparams > 0 && (!d_param_types || !d_param_name_off)) return RPCCRC_EINVAL;
-    if (name_bytes > 0 && !d_param_names) return RPCCRC_EINVAL;
-  } else if (nmethods > 0 && !d_result_types) {
-    return RPCCRC_EINVAL;
-  }
-  if (strings_bytes > 0 && !d_strings) return RPCCRC_EINVAL;
-  if (texts_bytes > 0 && !d_texts) return RPCCRC_EINVAL;
-  const uint32_t unit = params ? width : 1u;
-  if (n * unit >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  if (n == 0 && !d_total && !d_ndefer) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (d_ndefer) RPCCRC_TRY(hipMemsetAsync(d_ndefer, 0, sizeof(uint32_t), s));
-    return frames_layout_empty(d_total, nullptr, 0, s);
-  }
-  const uint64_t items = n * unit;
-  const size_t tmp_words = scan_tmp_words(items);
-  ValuesArgs a;
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    a.sizes = w.take<uint64_t>(items);
-    a.src_off = w.take<uint64_t>(items);
-    a.offs = w.take<uint64_t>(items + 1);
-    a.scan_tmp = w.take<uint64_t>(tmp_words);
-    a.text0 = w.take<uint64_t>(items);
-    a.text1 = w.take<uint64_t>(items);
-    a.text2 = w.take<uint64_t>(items);
-    a.long_off = w.take<uint64_t>(items);
-    a.meta = w.take<uint32_t>(items);
-    a.long_len = w.take<uint32_t>(items);
-    a.long_entry = w.take<uint32_t>(items);
-    a.long_bad = w.take<uint32_t>(items);
-    a.long_count = w.take<uint32_t>(1);
-    a.pre = w.take<uint8_t>(n);
-  });
-  if (rc) return rc;
-  a.form = form;
-  a.mode = d_mode;
-  a.status = d_status;
-  a.method = d_method;
-  a.slots = d_slots;
-  a.width = width;
-  a.n = n;
-  a.result_types = d_result_types;
-  a.param_first = d_param_first;
-  a.nmethods = nmethods;
-  a.param_types = d_param_types;
-  a.param_name_off = d_param_name_off;
-  a.nparams = params ? nparams : 0;
-  a.param_names = d_param_names;
-  a.name_bytes = params ? name_bytes : 0;
-  a.strings = d_strings;
-  a.strings_bytes = strings_bytes;
-  a.str_base = d_str_base;
-  a.texts = d_texts;
-  a.texts_bytes = texts_bytes;
-  a.text_off = d_text_offsets;
-  a.text_len = d_text_lens;
-  a.out = d_out;
-  a.out_cap = out_cap;
-  a.value_off = d_value_offsets;
-  a.value_len = d_value_lens;
-  a.values_status = d_values_status;
-  a.reply_status = d_reply_status;
-  a.ndefer = d_ndefer;
-  a.total = d_total;
-  a.unit = unit;
-  a.items = items;
-  return map_hip(launch_frames_values(a, s));
-}
-
-int rpc_frames_request_device(const uint16_t *d_method, const uint32_t *d_id, const uint16_t *d_types, uint64_t n,
-                              const uint8_t *d_method_names, uint32_t method_bytes, const uint32_t *d_method_off,
-                              uint32_t nmethods, const uint8_t *d_params, uint64_t params_bytes,
-                              const uint64_t *d_params_offsets, const uint32_t *d_params_lens,
-                              const uint64_t *d_conn_first, uint64_t nconn, uint8_t *d_out, uint64_t out_cap,
-                              uint64_t *d_body_offsets, uint32_t *d_body_lens, uint16_t *d_types_out,
-                              uint8_t *d_request_status, uint64_t *d_conn_bytes_first, uint64_t *d_total, void *stream) {
-  if (!frames_layout_args_ok(n, d_out, out_cap, d_conn_first, nconn, d_conn_bytes_first)) return RPCCRC_EINVAL;
-  if (nmethods > RPC_ROUTE_MAX_METHODS || method_bytes > RPC_ROUTE_MAX_METHOD_BYTES) return RPCCRC_EINVAL;
-  if (n > 0 && (!d_method || !d_id || !d_params_offsets || !d_params_lens)) return RPCCRC_EINVAL;
-  if (params_bytes > 0 && !d_params) return RPCCRC_EINVAL;
-  if (nmethods > 0 && !d_method_off) return RPCCRC_EINVAL;
-  if (method_bytes > 0 && !d_method_names) return RPCCRC_EINVAL;
-  if (n == 0 && !d_total && !d_conn_bytes_first) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n == 0) return frames_layout_empty(d_total, d_conn_bytes_first, nconn, s);
-  RequestArgs a;
-  Lease wsl;
-  rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-    const RequestWs ws = request_ws_layout(w, n, scan_tmp_words(n));
-    a.sizes = ws.sizes;
-    a.src_off = ws.src_off;
-    a.offs = ws.offs;
-    a.scan_tmp = ws.scan_tmp;
-    a.meta = ws.meta;
-    a.name_word = ws.name_word;
-  });
-  if (rc) return rc;
-  a.method = d_method;
-  a.id = d_id;
-  a.types = d_types;
-  a.n = n;
-  a.names = d_method_names;
-  a.method_bytes = method_bytes;
-  a.method_off = d_method_off;
-  a.nmethods = nmethods;
-  a.params = d_params;
-  a.params_bytes = params_bytes;
-  a.params_off = d_params_offsets;
-  a.params_len = d_params_lens;
-  a.conn_first = d_conn_first;
-  a.nconn = nconn;
-  a.out = d_out;
-  a.out_cap = out_cap;
-  a.body_off = d_body_offsets;
-  a.body_len = d_body_lens;
-  a.types_out = d_types_out;
-  a.request_status = d_request_status;
-  a.conn_bytes_first = d_conn_bytes_first;
-  a.total = d_total;
-  return map_hip(launch_frames_request(a, s));
-}
-
-int rpc_frames_resolve_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
-                              const uint32_t *d_body_lens, const uint16_t *d_reply_types, uint64_t n,
-                              const uint32_t *d_pending_ids, uint32_t npending, uint8_t *d_kind, uint32_t *d_id,
-                              uint32_t *d_result_off, uint32_t *d_result_len, uint32_t *d_error_off,
-                              uint32_t *d_error_len, uint32_t *d_slot, uint32_t *d_slot_entry, uint32_t *d_open,
-                              uint32_t *d_nopen, void *stream) {
-  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
-  if (npending > RPC_RESOLVE_MAX_PENDING) return RPCCRC_EINVAL;
-  if (n > 0 && (!d_body_offsets || !d_body_lens)) return RPCCRC_EINVAL;
-  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
-  if (npending > 0 && !d_pending_ids) return RPCCRC_EINVAL;
-  if ((d_open == nullptr) != (d_nopen == nullptr)) return RPCCRC_EINVAL;
-  if (n == 0 && !d_slot_entry && !d_nopen) return RPCCRC_OK;
-  DeviceCtx *c = nullptr;
-  int rc = get_async_ctx(&c);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ResolveArgs a;
-  a.slot = d_slot;
-  a.slot_entry = d_slot_entry;
-  Lease wsl;
-  if (npending) { // (the decode-only call joins nothing)
-    a.bits = resolve_table_bits(npending);
-    const size_t tmp_words = d_open ? scan_tmp_words(npending) : 0;
-    rc = wsl.get(c->ws, s, [&](WsLayout &w) {
-      if (d_open) {
-        a.flags = w.take<uint64_t>(npending);
-        a.offs = w.take<uint64_t>((uint64_t)npending + 1);
-        a.scan_tmp = w.take<uint64_t>(tmp_words);
-      }
-      a.cells = w.take<uint32_t>((uint64_t)1 << a.bits);
-      if (!d_slot_entry) a.slot_entry = w.take<uint32_t>(npending);
-      if (!d_slot && n) a.slot = w.take<uint32_t>(n);
-    });
-    if (rc) return rc;
-  }
-  a.bodies = d_bodies;
-  a.bodies_bytes = bodies_bytes;
-  a.body_off = d_body_offsets;
-  a.body_len = d_body_lens;
-  a.types = d_reply_types;
-  a.n = n;
-  a.pending = d_pending_ids;
-  a.npending = npending;
-  a.kind = d_kind;
-  a.id = d_id;
-  a.result_off = d_result_off;
-  a.result_len = d_result_len;
-  a.error_off = d_error_off;
-  a.error_len = d_error_len;
-  a.open = d_open;
-  a.nopen = d_nopen;
-  return map_hip(launch_frames_resolve(a, s));
-}
-
-int rpc_frames_scan_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
-                           const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
-                           uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first, uint64_t *d_conn_consumed,
-                           uint8_t *d_conn_state, uint64_t *d_nframes, void *stream) {
-  return frames_scan_common(d_stream, stream_bytes, d_conn_off, d_conn_len, nconn, flags, d_frame_offsets, d_frame_conn,
-                            frame_cap, d_conn_first, d_conn_consumed, d_conn_state, d_nframes, nullptr, nullptr, false,
-                            stream);
-}
-
-int rpc_frames_scan_verify_device(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_conn_off,
-                                  const uint64_t *d_conn_len, uint64_t nconn, int flags, uint64_t *d_frame_offsets,
-                                  uint32_t *d_frame_conn, uint64_t frame_cap, uint64_t *d_conn_first,
-                                  uint64_t *d_conn_consumed, uint8_t *d_conn_state, uint64_t *d_nframes,
-                                  uint8_t *d_verdict, uint32_t *d_crc, void *stream) {
-  return frames_scan_common(d_stream, stream_bytes, d_conn_off, d_conn_len, nconn, flags, d_frame_offsets, d_frame_conn,
-                            frame_cap, d_conn_first, d_conn_consumed, d_conn_state, d_nframes, d_verdict, d_crc, true,
-                            stream);
-}
-
-int rpc_frames_set_scan_path(int path) {
-  if (path != RPCCRC_SCAN_AUTO && path != RPCCRC_SCAN_SERIAL && path != RPCCRC_SCAN_TILED) return RPCCRC_EINVAL;
-  g_scan_path.store(path);
-  return RPCCRC_OK;
-}
 
 uint32_t rpc_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) { return crc32_combine(crc1, crc2, len2); }
 
