@@ -926,6 +926,107 @@ RPCCRC_API int rpc_frames_args_device(const uint8_t *d_bodies, uint64_t bodies_b
                            const uint8_t *d_param_names, uint32_t name_bytes, uint32_t width,
                            uint64_t *d_slots, uint8_t *d_status, int32_t *d_reply_status, void *stream);
 
+/* ---- frame results: typed results decoded per pending slot --------------------
+ * What sits between a client's resolve and its completions: the args' mirror on
+ * the client side.  The reference's generated client stubs
+ * (client/gen/rpc_client_gen.c) read the `result` member that
+ * rpc_codec_decode_response hands over in one of five fixed shapes, one per IDL
+ * result type -- cJSON_IsString -> the string; cJSON_IsString -> strtoll, or
+ * cJSON_IsNumber -> (int64_t)valuedouble; cJSON_IsNumber -> (int32_t)valuedouble;
+ * cJSON_IsNumber -> valuedouble; cJSON_IsBool -> cJSON_IsTrue -- return their
+ * default (0, 0.0, false, NULL) in every other case and never look at `error`.
+ * This call does that for every MATCHED entry of a resolve and leaves the
+ * completions indexed by pending slot, so that only columns cross to the host.
+ * Like the args it is not a JSON codec: inside its strict subset the answer is
+ * the reference's, everything else reads RPC_RESULTS_DEFER and goes through the
+ * host's parser on the span as before.
+ * d_bodies, d_body_offsets, d_body_lens are the unpack's outputs; d_kind,
+ * d_slot, d_result_off, d_result_len, d_error_off, d_error_len, d_slot_entry
+ * the resolve's, all unchanged.  d_pending_method[s] (npending words) is the
+ * method index slot s's request was sent with -- the d_method given to
+ * rpc_frames_request_device -- and d_result_types[m] (nmethods bytes, RPC_ARG_*)
+ * the array rpc_frames_values_device's RESULT form takes.
+ * For entry i, in this order:
+ *   1. d_kind[i] != RPC_RESOLVE_MATCHED: RPC_RESULTS_NONE.  Nothing else of the
+ *      entry is looked at (pending_take finds nothing for an UNKNOWN or a
+ *      DUPLICATE reply: the reference drops it).
+ *   2. RPC_RESULTS_BAD_SCHEMA, with no body byte read, if d_slot[i] >= npending;
+ *      if d_pending_method[d_slot[i]] >= nmethods; if that method's type is not
+ *      an RPC_ARG_*.
+ *   3. RPC_RESULTS_RANGE, with nothing read, if the body does not lie inside
+ *      [0, bodies_bytes) or one of the two spans does not lie inside the body
+ *      (all computed without wrap).  A span of length 0 is not checked.
+ *   4. d_result_len[i] == 0: RPC_RESULTS_ABSENT, value 0 (no `result`: the
+ *      reference returns the default).
+ *   5. RPC_RESULTS_DEFER unless the span is one strict JSON value: rule 6 of
+ *      rpc_frames_args_device word for word, with its three limits.  A body
+ *      longer than RPC_ROUTE_MAX_BODY defers as well (it is not staged), and so
+ *      does an object with a backslash in a depth-1 key (the args' rule 8 rides
+ *      along with their walk; the host's answer is the default either way).
+ *   6. The value's JSON type, judged from its first byte alone, against the
+ *      declared type: a number takes I32, I64, F64; a string takes STR and I64;
+ *      true / false takes BOOL; null, an object and an array take none.  A
+ *      value the type does not take: RPC_RESULTS_MISMATCH, value 0 -- the
+ *      default the reference returns, also for the null its server prints for
+ *      a NaN or an infinity.
+ *   7. The conversion of rpc_frames_args_device's rule 10 word for word, with
+ *      every DEFER class it names: I32, I64, F64 from a number; I64 from a
+ *      string; BOOL; STR as offset | (uint64_t)length << 32 of the bytes
+ *      between the quotes, the offset relative to the body's first byte, where
+ *      a backslash inside is DEFER.  RPC_RESULTS_OK with the value, or
+ *      RPC_RESULTS_DEFER with value 0.
+ * `error` is decoded independently of the value, with a status of its own in
+ * the same codes.  d_error_len[i] == 0: ABSENT.  Else the span goes through
+ * rules 6-10 of rpc_frames_args_device as if it were the `params` of a method
+ * declaring (code: I32, message: STR): OK there is OK here, with d_error_code[i]
+ * and d_error_message[i] (offset | length << 32, relative to the body);
+ * INVALID there is MISMATCH, DEFER is DEFER, both with zeros.  (A span inside a
+ * body longer than RPC_ROUTE_MAX_BODY: DEFER.)  An entry whose status is NONE,
+ * BAD_SCHEMA or RANGE has error status ABSENT and zeros.
+ * Per slot s, with e = d_slot_entry[s]: if e < n, d_kind[e] ==
+ * RPC_RESOLVE_MATCHED and d_slot[e] == s, then d_slot_status[s],
+ * d_slot_value[s], d_slot_error_status[s] and d_slot_error_code[s] are entry
+ * e's answers and d_slot_str_base[s] is d_body_offsets[e] -- the d_str_base of
+ * rpc_frames_values_device, so that a STR completion can be echoed where it
+ * lies.  Otherwise the slot is open and all five read 0.  At most one entry
+ * passes that test for a slot, whatever the input (two MATCHED entries naming
+ * one slot among them): the answer does not depend on the order in which lanes
+ * or workgroups run.
+ * *d_ndefer is the number of entries whose status or error status is DEFER,
+ * each counted once: non-zero tells the host to parse those spans.
+ * Nothing outside [d_bodies, d_bodies + bodies_bytes), the two schema arrays
+ * and the listed inputs is read, not even by an aligned load window.  All
+ * pointers are device pointers; every output is optional; the call is
+ * asynchronous on `stream` and needs no workspace.
+ * RPCCRC_EINVAL, before any device is touched: n >= 0xFFFFFFFF; npending >
+ * RPC_RESOLVE_MAX_PENDING; nmethods > RPC_ROUTE_MAX_METHODS; n > 0 with
+ * d_body_offsets, d_body_lens, d_kind, d_slot, d_result_off, d_result_len,
+ * d_error_off or d_error_len NULL; bodies_bytes > 0 with d_bodies NULL;
+ * npending > 0 with d_pending_method NULL; nmethods > 0 with d_result_types
+ * NULL; a per-slot output given without d_slot_entry.  n == 0 still writes the
+ * per-slot outputs (every slot open) and *d_ndefer = 0 when they are given and
+ * is otherwise RPCCRC_OK with no device touched. */
+#define RPC_RESULTS_NONE 0u       /* not a MATCHED entry; an open slot */
+#define RPC_RESULTS_OK 1u         /* the member decoded */
+#define RPC_RESULTS_ABSENT 2u     /* the reply has no such member: the default */
+#define RPC_RESULTS_MISMATCH 3u   /* a JSON type the declared type does not take: the default */
+#define RPC_RESULTS_DEFER 4u      /* outside the strict subset: the host's parser decides */
+#define RPC_RESULTS_RANGE 5u      /* the body or a span lies outside its buffer: nothing read */
+#define RPC_RESULTS_BAD_SCHEMA 6u /* no such slot, method or type: no body byte read */
+RPCCRC_API int rpc_frames_results_device(const uint8_t *d_bodies, uint64_t bodies_bytes,
+                           const uint64_t *d_body_offsets, const uint32_t *d_body_lens,
+                           const uint8_t *d_kind, const uint32_t *d_slot,
+                           const uint32_t *d_result_off, const uint32_t *d_result_len,
+                           const uint32_t *d_error_off, const uint32_t *d_error_len,
+                           const uint32_t *d_slot_entry, uint64_t n,
+                           const uint16_t *d_pending_method, uint32_t npending,
+                           const uint8_t *d_result_types, uint32_t nmethods,
+                           uint8_t *d_status, uint64_t *d_value, uint8_t *d_error_status,
+                           int32_t *d_error_code, uint64_t *d_error_message,
+                           uint8_t *d_slot_status, uint64_t *d_slot_value, uint8_t *d_slot_error_status,
+                           int32_t *d_slot_error_code, uint64_t *d_slot_str_base,
+                           uint32_t *d_ndefer, void *stream);
+
 /* ---- frame values: typed results and params as JSON text ---------------------
  * The args' mirror: what sits between the handlers' typed columns and
  * rpc_frames_reply_device, and between a client's columns and

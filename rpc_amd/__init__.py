@@ -29,10 +29,10 @@ from .rx_ring import RxRing
 from .constants import *  # noqa: F401,F403
 from ._device import _dev_u32_out, _read_back, _stream_handle, _torch  # noqa: F401
 from .frames import (  # noqa: F401
-    SCAN_PATHS, ArgsSchema, FrameArgs, FrameCarry, FramePack, FrameReply, FrameRequest, FrameResolve, FrameRoute,
-    FrameScan, FrameUnpack, FrameValues, RouteTable, args_schema, carry_slots, frames_args, frames_carry, frames_pack,
-    frames_reply, frames_request, frames_resolve, frames_route, frames_scan, frames_stamp, frames_unpack, frames_values,
-    frames_verify, result_types, route_table, set_scan_path,
+    SCAN_PATHS, ArgsSchema, FrameArgs, FrameCarry, FramePack, FrameReply, FrameRequest, FrameResolve, FrameResults,
+    FrameRoute, FrameScan, FrameUnpack, FrameValues, RouteTable, args_schema, carry_slots, frames_args, frames_carry,
+    frames_pack, frames_reply, frames_request, frames_resolve, frames_results, frames_route, frames_scan, frames_stamp,
+    frames_unpack, frames_values, frames_verify, result_types, route_table, set_scan_path,
 )
 
 __all__ = [
@@ -134,6 +134,15 @@ __all__ = [
     "RESOLVE_RANGE",
     "RESOLVE_NO_SLOT",
     "RESOLVE_MAX_PENDING",
+    "frames_results",
+    "FrameResults",
+    "RESULTS_NONE",
+    "RESULTS_OK",
+    "RESULTS_ABSENT",
+    "RESULTS_MISMATCH",
+    "RESULTS_DEFER",
+    "RESULTS_RANGE",
+    "RESULTS_BAD_SCHEMA",
     "frames_reply",
     "FrameReply",
     "REPLY_NONE",

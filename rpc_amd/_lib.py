@@ -80,6 +80,8 @@ rpc_frames_resolve_device = _sig("rpc_frames_resolve_device", _i32, _vp, _u64, _
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_args_device = _sig("rpc_frames_args_device", _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp,
                               _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp)
+rpc_frames_results_device = _sig("rpc_frames_results_device", _i32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _u64, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_reply_device = _sig("rpc_frames_reply_device", _i32, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp,
                                _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
 rpc_frames_request_device = _sig("rpc_frames_request_device", _i32, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _u64, _vp,
@@ -139,6 +141,7 @@ EXPORTS = (
     "rpc_frames_route_device",
     "rpc_frames_resolve_device",
     "rpc_frames_args_device",
+    "rpc_frames_results_device",
     "rpc_frames_reply_device",
     "rpc_frames_request_device",
     "rpc_frames_values_device",

@@ -19,6 +19,7 @@
 #include "frames_reply.h"
 #include "frames_request.h"
 #include "frames_resolve.h"
+#include "frames_results.h"
 #include "frames_route.h"
 #include "frames_scan.h"
 #include "frames_unpack.h"
@@ -426,6 +427,60 @@ int rpc_frames_args_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const
   a.status = d_status;
   a.reply_status = d_reply_status;
   return map_hip(launch_frames_args(a, f.s));
+}
+
+int rpc_frames_results_device(const uint8_t *d_bodies, uint64_t bodies_bytes, const uint64_t *d_body_offsets,
+                              const uint32_t *d_body_lens, const uint8_t *d_kind, const uint32_t *d_slot,
+                              const uint32_t *d_result_off, const uint32_t *d_result_len, const uint32_t *d_error_off,
+                              const uint32_t *d_error_len, const uint32_t *d_slot_entry, uint64_t n,
+                              const uint16_t *d_pending_method, uint32_t npending, const uint8_t *d_result_types,
+                              uint32_t nmethods, uint8_t *d_status, uint64_t *d_value, uint8_t *d_error_status,
+                              int32_t *d_error_code, uint64_t *d_error_message, uint8_t *d_slot_status,
+                              uint64_t *d_slot_value, uint8_t *d_slot_error_status, int32_t *d_slot_error_code,
+                              uint64_t *d_slot_str_base, uint32_t *d_ndefer, void *stream) {
+  if (n >= 0xFFFFFFFFull) return RPCCRC_EINVAL;
+  if (npending > RPC_RESOLVE_MAX_PENDING || nmethods > RPC_ROUTE_MAX_METHODS) return RPCCRC_EINVAL;
+  if (n > 0 && (!d_body_offsets || !d_body_lens || !d_kind || !d_slot || !d_result_off || !d_result_len ||
+                !d_error_off || !d_error_len))
+    return RPCCRC_EINVAL;
+  if (bodies_bytes > 0 && !d_bodies) return RPCCRC_EINVAL;
+  if (npending > 0 && !d_pending_method) return RPCCRC_EINVAL;
+  if (nmethods > 0 && !d_result_types) return RPCCRC_EINVAL;
+  const bool per_slot = d_slot_status || d_slot_value || d_slot_error_status || d_slot_error_code || d_slot_str_base;
+  if (per_slot && !d_slot_entry) return RPCCRC_EINVAL;
+  if (n == 0 && !d_ndefer && !(per_slot && npending)) return RPCCRC_OK;
+  FramesCall f;
+  const int rc = f.open(stream);
+  if (rc) return rc;
+  ResultsArgs a; // (no workspace; with n == 0 every slot is open and nothing defers)
+  a.bodies = d_bodies;
+  a.bodies_bytes = bodies_bytes;
+  a.body_off = d_body_offsets;
+  a.body_len = d_body_lens;
+  a.kind = d_kind;
+  a.slot = d_slot;
+  a.result_off = d_result_off;
+  a.result_len = d_result_len;
+  a.error_off = d_error_off;
+  a.error_len = d_error_len;
+  a.slot_entry = d_slot_entry;
+  a.n = n;
+  a.pending_method = d_pending_method;
+  a.npending = npending;
+  a.result_types = d_result_types;
+  a.nmethods = nmethods;
+  a.status = d_status;
+  a.value = d_value;
+  a.error_status = d_error_status;
+  a.error_code = d_error_code;
+  a.error_message = d_error_message;
+  a.slot_status = d_slot_status;
+  a.slot_value = d_slot_value;
+  a.slot_error_status = d_slot_error_status;
+  a.slot_error_code = d_slot_error_code;
+  a.slot_str_base = d_slot_str_base;
+  a.ndefer = d_ndefer;
+  return map_hip(launch_frames_results(a, f.s));
 }
 
 int rpc_frames_reply_device(const uint8_t *d_kind, const uint32_t *d_id, const int32_t *d_status,

@@ -1,5 +1,5 @@
 """The frame stages of include/rpccrc.h on device tensors: verify, stamp, scan, unpack, carry,
-route, args, resolve, values, reply, request and pack, with their result types and the builders
+route, args, resolve, results, values, reply, request and pack, with their result types and the builders
 of the method table and the parameter schema.  ``rpc_amd`` re-exports all of it.
 
 Every wrapper checks its tensors, allocates its outputs and makes one call of ``_lib.<entry>``,
@@ -504,6 +504,73 @@ def frames_resolve(bodies, body_offsets, body_lens, pending_ids=None, reply_type
                                          _ptr(slot_entry), opened.data_ptr(), nopen.data_ptr(), _stream_handle(stream)),
           "rpc_frames_resolve_device")
     return FrameResolve(kind, rid, roff, rlen, eoff, elen, slot, slot_entry, opened[:npending], nopen)
+
+
+class FrameResults(NamedTuple):
+    """What frames_results returns (device tensors; nothing is read back)."""
+    status: object             # uint8 [n]: RESULTS_NONE / _OK / _ABSENT / _MISMATCH / _DEFER / _RANGE / _BAD_SCHEMA
+    value: object              # int64 [n]: the typed `result` (F64: .view(torch.float64)), 0 unless RESULTS_OK
+    error_status: object       # uint8 [n]: the `error` member's status, same codes
+    error_code: object         # int32 [n]: its `code`, 0 unless RESULTS_OK
+    error_message: object      # int64 [n]: its `message` as offset | length << 32 into the body
+    slot_status: object        # uint8 [npending]: the completing entry's status, 0 (RESULTS_NONE) while the slot is open
+    slot_value: object         # int64 [npending]
+    slot_error_status: object  # uint8 [npending]
+    slot_error_code: object    # int32 [npending]
+    slot_str_base: object      # int64 [npending]: the completing entry's body offset: frames_values' ``str_base``
+    ndefer: object             # int32 [1]: entries whose status or error status is RESULTS_DEFER
+
+
+def frames_results(bodies, body_offsets, body_lens, resolve: FrameResolve, pending_method, result_types,
+                   stream=None) -> FrameResults:
+    """The typed result of every matched reply, per entry and per pending slot
+    (rpc_frames_results_device): what sits between a client's ``frames_resolve`` and its
+    completions.
+
+    ``bodies, body_offsets, body_lens`` are ``frames_unpack``'s outputs and ``resolve`` is
+    ``frames_resolve``'s, all unchanged.  ``pending_method[s]`` (a 2-byte tensor beside
+    ``pending_ids``) is the method slot ``s``'s request was sent with -- ``frames_request``'s
+    ``method`` -- and ``result_types`` (``result_types(...)``) holds each method's result type.
+    Per MATCHED entry the ``result`` span is converted as the reference's generated client reads
+    it: an I32 / I64 / BOOL value is the value, an F64 value the double's bits, a STR value
+    ``offset | length << 32`` of the bytes between the quotes, relative to the body's first byte;
+    a missing member (RESULTS_ABSENT) or one of the wrong JSON type (RESULTS_MISMATCH) reads the
+    default, 0.  The ``error`` member is decoded beside it into ``code`` and ``message``.  The
+    ``slot_*`` columns hold the same answers indexed by pending slot, 0 while a slot stays open.
+    Spans outside the strict subset of include/rpccrc.h read RESULTS_DEFER: parse those on the
+    host as before (``json.loads`` on the span); ``ndefer`` says whether there are any."""
+    t = _torch()
+    n = body_offsets.numel()
+    _check_tensors("n", n, (("body_offsets", body_offsets, 8), ("body_lens", body_lens, 4), ("resolve.kind", resolve.kind, 1),
+                            ("resolve.slot", resolve.slot, 4), ("resolve.result_off", resolve.result_off, 4),
+                            ("resolve.result_len", resolve.result_len, 4), ("resolve.error_off", resolve.error_off, 4),
+                            ("resolve.error_len", resolve.error_len, 4)))
+    _check_bytes("bodies", bodies)
+    npending = 0 if pending_method is None else pending_method.numel()
+    if npending > RESOLVE_MAX_PENDING:
+        raise ValueError(f"at most {RESOLVE_MAX_PENDING} pending slots")
+    _check_tensors("npending", npending, (("pending_method", pending_method, 2), ("resolve.slot_entry", resolve.slot_entry, 4)),
+                   optional=("pending_method",))
+    if result_types.element_size() != 1 or not result_types.is_contiguous() or result_types.numel() > ROUTE_MAX_METHODS:
+        raise ValueError(f"result_types must be a contiguous 1-byte tensor of at most {ROUTE_MAX_METHODS} elements")
+    dev = bodies.device
+    status, estatus = (t.empty(n, dtype=t.uint8, device=dev) for _ in range(2))
+    value, emsg = (t.empty(n, dtype=t.int64, device=dev) for _ in range(2))
+    ecode = t.empty(n, dtype=t.int32, device=dev)
+    s_status, s_estatus = (t.empty(npending, dtype=t.uint8, device=dev) for _ in range(2))
+    s_value, s_base = (t.empty(npending, dtype=t.int64, device=dev) for _ in range(2))
+    s_ecode = t.empty(npending, dtype=t.int32, device=dev)
+    ndefer = t.empty(1, dtype=t.int32, device=dev)
+
+    check(_lib.rpc_frames_results_device(_ptr(bodies), _count(bodies), _ptr(body_offsets), _ptr(body_lens),
+                                         _ptr(resolve.kind), _ptr(resolve.slot), _ptr(resolve.result_off),
+                                         _ptr(resolve.result_len), _ptr(resolve.error_off), _ptr(resolve.error_len),
+                                         _ptr(resolve.slot_entry), n, _ptr(pending_method), npending, _ptr(result_types),
+                                         result_types.numel(), _ptr(status), _ptr(value), _ptr(estatus), _ptr(ecode),
+                                         _ptr(emsg), _ptr(s_status), _ptr(s_value), _ptr(s_estatus), _ptr(s_ecode),
+                                         _ptr(s_base), ndefer.data_ptr(), _stream_handle(stream)),
+          "rpc_frames_results_device")
+    return FrameResults(status, value, estatus, ecode, emsg, s_status, s_value, s_estatus, s_ecode, s_base, ndefer)
 
 
 class FrameReply(NamedTuple):
